@@ -134,6 +134,43 @@ def pmc_traffic(kernel=None):
     return sum(n * one(k) * prof[k].get('launch_fraction_of_envs', 1.0) for k, n in per_step.items())
 
 
+DUMP_BYTES_MAX = 64 << 20     # --dump-outputs: larger outputs are cut to a fixed, seeded sample of their rows
+
+
+def host_outputs(step_out, extra=None):
+    """what a caller of env.step received in a step - obs dict, reward, done, info dict (+ `extra` arrays) - copied to the host by name, before the next
+    step overwrites the env's buffers; integer and bool arrays become float64 (exact), floating ones float32"""
+    obs, r, done, info = step_out
+    named = [('obs_' + k, v) for k, v in obs.items()] + [('reward', r), ('done', done)] + [('info_' + k, v) for k, v in info.items()]
+    named += sorted((extra or {}).items())
+    out = {}
+    for name, t in named:
+        if t is not None:
+            t = t.detach().cpu()
+            out[name] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    return out
+
+
+def write_outputs(out_dir, arrays, seed=1234):
+    """DIR/<name>.npy for every array; over DUMP_BYTES_MAX in all, every array keeps the same share of its rows, picked by a seeded draw per row count
+    (the rows kept of arrays with R rows are listed in DIR/sampled_rows_of_<R>.npy)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        share = 0.95 * DUMP_BYTES_MAX / (total + 8 * sum({a.shape[0] for a in arrays.values()}))     # (+ the float64 row lists; 5 % for the .npy headers)
+        picked = {}
+        for name, a in list(arrays.items()):
+            rows = a.shape[0]
+            if rows not in picked:
+                picked[rows] = np.sort(np.random.default_rng(seed).choice(rows, size=max(1, int(rows * share)), replace=False))
+            arrays[name] = a[picked[rows]]
+        for rows, idx in picked.items():
+            arrays['sampled_rows_of_%d' % rows] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def sharding_offset(rank, world, n):
     from roboticsplayroompybullet_amd import sharding
     return sharding.shard_range(rank, world, n)[0]
@@ -143,7 +180,7 @@ def cem_region(env, starts, iterations, device, seed):
     """BASELINE config C5, one timed region: `iterations` CEM iterations over CEM_GOALS start states (rows of rp_get_state, contact caches included) x CEM_CANDIDATES
     candidate action sequences of CEM_HORIZON steps.  Per iteration: every start state is broadcast to its 512 envs (rp_set_state), the candidates are drawn around the
     running mean / deviation of their start state, rolled out open loop, the rewards summed per candidate ON THE DEVICE, the best CEM_ELITES refit mean and deviation.
-    Returns (env steps taken, seconds, the last iteration's best return per start state)."""
+    Returns (env steps taken, seconds, the last iteration's best return per start state, what the last env.step returned)."""
     n = env.num_envs
     g = torch.Generator(device=device).manual_seed(seed)
     lo, hi = (torch.tensor(v, device=device) for v in B_RANGES[ENV_ID])
@@ -160,15 +197,15 @@ def cem_region(env, starts, iterations, device, seed):
         plan = acts.permute(2, 0, 1, 3).reshape(CEM_HORIZON, n, 7).contiguous()
         ret = torch.zeros(n, device=device)
         for t in range(CEM_HORIZON):
-            _, r, _, _ = env.step(plan[t])
-            ret += r                                                                 # (the reward buffer is overwritten by the next step)
+            last = env.step(plan[t])
+            ret += last[1]                                                           # (the reward buffer is overwritten by the next step)
         ret = ret.view(CEM_GOALS, CEM_CANDIDATES)
         top = ret.topk(CEM_ELITES, dim=1).indices                                   # [goal, elite]
         elite = torch.gather(acts, 1, top[:, :, None, None].expand(-1, -1, CEM_HORIZON, 7))
         mu, sd = elite.mean(1), elite.std(1) + 1e-3
         best = ret.max(1).values
     torch.cuda.synchronize()
-    return iterations * CEM_HORIZON, time.perf_counter() - t0, best
+    return iterations * CEM_HORIZON, time.perf_counter() - t0, best, last
 
 
 def main():
@@ -185,6 +222,9 @@ def main():
     ap.add_argument('--stateless-contacts', action='store_true', help='RP_CFG_STATELESS_CONTACTS: no contact cache (round 3\'s first model)')
     ap.add_argument('--repeats', type=int, default=3, help='timed regions of --steps steps; `value` is the first one, the median is reported beside it')
     ap.add_argument('--no-extras', action='store_true', help='skip distribution A and the second contact margin')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last step of the measured region returned (obs, reward, done, info; C5: also the best return per start state; N > 1: also '
+                         'the gathered pack) as DIR/<name>.npy in float32 / float64, at most 64 MB in all; same arguments, same inputs')
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     env_id = cfg['env_id']
@@ -239,7 +279,8 @@ def main():
         """EXACTLY `steps` env steps between barrier + synchronize on both sides; returns the max over ranks of the wall seconds.
         For N > 1 the only collective on the path - the all-gather of env.pack (obs_quat | achieved_goal | reward | is_success,
         written in that layout by k_calc_state itself) - is enqueued asynchronously after every step, so the gather of step k runs
-        on RCCL's stream while step k + 1's physics runs on ours; every gather is complete inside the region."""
+        on RCCL's stream while step k + 1's physics runs on ours; every gather is complete inside the region.
+        Also returns what the last env.step returned (views of the env's buffers: the next step overwrites them)."""
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -248,7 +289,7 @@ def main():
         if events:
             events[0].record()                 # ONE pair around the whole region (a pair per step puts two marker packets into the queue per step: 2 % of the step)
         for k in range(steps):
-            obs, r, done, info = env.step(acts[first + k])
+            last = env.step(acts[first + k])
             if world > 1:
                 if pending is not None:
                     pending.wait()
@@ -265,7 +306,7 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        return elapsed, info
+        return elapsed, last[3], last
 
     for a in list(pre_actions) + [actions[k] for k in range(args.warmup)]:
         env.step(a)
@@ -281,7 +322,7 @@ def main():
         iters = max(1, args.steps // CEM_HORIZON)
         cem_region(env, starts, 1, device, 99)                  # (one untimed iteration: allocator, clocks)
         ev0.record()
-        steps_done, elapsed, best = cem_region(env, starts, iters, device, 100)
+        steps_done, elapsed, best, last = cem_region(env, starts, iters, device, 100)
         ev1.record()
         torch.cuda.synchronize()
         info = {'status': env.buf['status'], 'is_success': env.buf['is_success']}
@@ -291,8 +332,14 @@ def main():
                        'per-candidate return summed on the device, top-64 refit of mean and deviation; `steps` = iterations x 50'}
         args.steps = steps_done
     else:
-        elapsed, info = timed_region(env, actions, args.warmup, args.steps, (ev0, ev1))       # the contract's region: `value`
+        elapsed, info, last = timed_region(env, actions, args.warmup, args.steps, (ev0, ev1))       # the contract's region: `value`
     torch.cuda.synchronize()
+    dump = None
+    if args.dump_outputs and rank == 0:          # the region's last step, copied before anything steps the env again
+        extra = {'cem_best_return': best} if cem else {}
+        if world > 1:
+            extra['gathered_pack'] = gathered
+        dump = host_outputs(last, extra)
     step_ms = ev0.elapsed_time(ev1) / args.steps      # device-side time of the same region (events on rp_step's stream)
     # per-launch kernel durations: hipEvent pairs recorded on the launch stream inside rp_step; bracketing single kernels
     # needs the env groups (concurrent streams) switched off, so this is a second region over the same actions
@@ -313,7 +360,7 @@ def main():
     if n_rep:      # FRESH actions per repeat (round 5: replaying the first region's twenty actions let the arms settle near the same targets - each repeat 1 - 2 % faster than the one before)
         more = make_actions(n, n_rep * args.steps, device, 9000 + rank, env_id)
     for i in range(n_rep):
-        t_rep, _ = timed_region(env, more, i * args.steps, args.steps)
+        t_rep, _, _ = timed_region(env, more, i * args.steps, args.steps)
         rep_values.append(global_envs * args.steps / t_rep)
     extras = {}
     if not args.no_extras and world == 1 and cem is None:
@@ -322,7 +369,7 @@ def main():
         acts_a = (2 * torch.rand((pre + args.warmup + args.steps, n, 7), generator=g, device=device) - 1) * hi
         for k in range(pre + args.warmup):          # the same floor of untimed steps for this distribution (other actions, other contact sets), every step on actions of its own
             env.step(acts_a[k])
-        t_a, info_a = timed_region(env, acts_a, pre + args.warmup, args.steps)
+        t_a, info_a, _ = timed_region(env, acts_a, pre + args.warmup, args.steps)
         extras['distribution_A'] = {'value': n * args.steps / t_a, 'ms_per_step': 1e3 * t_a / args.steps,
                                     'what': 'a ~ U(action_space.low, action_space.high) = U(-6, 6)^6 x U(-1, 1), resampled every step (the '
                                             'literal random-action rollout: targets mostly unreachable, the arm slews at the per-step clip); continues from the headline rollout, %d untimed steps of this '
@@ -336,7 +383,7 @@ def main():
             env2.reset()
             for a in list(pre_actions) + [actions[k] for k in range(args.warmup)]:
                 env2.step(a)
-            t_m, _ = timed_region(env2, actions, args.warmup, args.steps)
+            t_m, _, _ = timed_region(env2, actions, args.warmup, args.steps)
             extras['contact_margin_%g' % other] = {'value': n * args.steps / t_m, 'ms_per_step': 1e3 * t_m / args.steps,
                                                    'what': 'the same workload with rp_config.contact_margin = %g m for every pair' % other}
             env2.close()
@@ -402,6 +449,8 @@ def main():
         line.update(extras)
         if world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(1234, args.contact_margin, env_id)
+        if dump is not None:
+            write_outputs(args.dump_outputs, dump)
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

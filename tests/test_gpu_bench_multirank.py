@@ -94,6 +94,25 @@ def test_bench_strong_scaling_two_ranks_gloo_on_one_device():
     assert abs(d['value'] - 1025 * 4 / (d['ms_per_step'] * 4e-3)) < 1e-6 * d['value'] and d['non_finite_envs'] == 0
 
 
+def test_bench_dump_outputs_repeat_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last step of the measured region as DIR/<name>.npy (float32 / float64, one row per env, at most 64 MB in all); two runs with the
+    same arguments write the same arrays bit for bit (seeded inputs, a deterministic library), so that two builds can be compared output for output"""
+    import numpy as np
+    args = ['--steps', '4', '--warmup', '1', '--no-extras', '--no-cpu-baseline', '--repeats', '1', '--envs-per-gpu', '512', '--dump-outputs']
+    runs = [(run_bench(args + [str(tmp_path / d)]), tmp_path / d) for d in ('a', 'b')]
+    for d, _ in runs:
+        assert d['steps'] == 4 and d['ms_per_step'] > 0 and d['non_finite_envs'] == 0
+    files = sorted(os.listdir(runs[0][1]))
+    assert files == sorted(os.listdir(runs[1][1]))
+    assert {'obs_obs_quat.npy', 'obs_achieved_goal.npy', 'reward.npy', 'done.npy', 'info_status.npy', 'info_is_success.npy'} <= set(files)
+    assert sum(os.path.getsize(runs[0][1] / f) for f in files) <= 64 << 20
+    for f in files:
+        a, b = np.load(runs[0][1] / f), np.load(runs[1][1] / f)
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 512, (f, a.dtype, a.shape)
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f
+    assert np.isfinite(np.load(runs[0][1] / 'obs_obs_quat.npy')).all()
+
+
 @pytest.mark.parametrize('config,env_id,envs', [('C2', 'UR5PlayAbsRPY1Obj-v0', 1024), ('C3', 'pandaPick-v0', 4096), ('C5', 'UR5PlayAbsRPY1Obj-v0', 16384)])
 def test_bench_prints_the_same_line_for_every_baseline_config(config, env_id, envs):
     """bench.py --config {C2, C3, C5}: BASELINE.json's other configs through the same protocol, the same JSON shape (roofline with that config's algorithmic bytes,

@@ -1,6 +1,8 @@
 import os, sys
 import numpy as np, torch
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/oracle'); sys.path.insert(0, '/root/repo/tools'); sys.path.insert(0, '/root/repo/tests')
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ('', 'oracle', 'tools', 'tests'):
+    sys.path.insert(0, os.path.join(REPO, p))
 from oracle import OracleEnv
 from roboticsplayroompybullet_amd import VecPlayEnv
 from gpu_debug import record_from_oracle

@@ -1,5 +1,6 @@
-import sys, numpy as np, torch
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/oracle')
+import os, sys, numpy as np, torch
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, 'oracle'))
 from oracle import OracleEnv
 from roboticsplayroompybullet_amd import VecPlayEnv
 ID = 'UR5PlayAbsRPY1Obj-v0'

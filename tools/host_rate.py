@@ -1,5 +1,5 @@
 import sys, time, os, torch
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from roboticsplayroompybullet_amd import VecPlayEnv
 n = 4096
