@@ -11,7 +11,7 @@
  *     (float32 unless noted), valid until `stream` reaches the call; the library owns only its internal state.
  *   - a handle is bound to one device, is not thread-safe, and enqueues on the caller's stream
  *     (pass torch.cuda.current_stream().cuda_stream); `stream` is a hipStream_t passed as void*.
- *   - no host<->device copies and no synchronisation inside rp_step / rp_reset_to / rp_compute_reward; rp_reset reads one
+ *   - no host<->device copies and no synchronisation inside rp_step / rp_step_autoreset / rp_reset_to / rp_compute_reward; rp_reset reads one
  *     4-byte counter back per round of settle substeps (see rp_reset).  (Debug path only: with rp_set_fused(h, 1) AND timers
  *     enabled, rp_step waits for its own kernel to read the timer - rp_playroom_debug.h.)
  *   - every entry point makes the handle's device current for the duration of the call and restores the caller's device,
@@ -243,6 +243,28 @@ int rp_render_ex(rp_handle h, const rp_camera* cam, int32_t width, int32_t heigh
  * index of an arm collider, -1 otherwise), hit_position [N, k, 3], hit_normal [N, k, 3].  A ray that starts inside a shape does not hit it. */
 int rp_ray_test(rp_handle h, const float* from, const float* to, int32_t k, float* hit_fraction, int32_t* collider, int32_t* link,
                 float* hit_position, float* hit_normal, void* stream);
+
+/* ---- episodes ended on the device (0.5) ---------------------------------------------------------------------------------------------
+ * rp_step_autoreset steps every env as rp_step does (whatever rp_set_fused / rp_set_groups chose) and then resets the envs whose episode ended,
+ * on the device: nothing is read back, nothing synchronises, the call returns once the work is enqueued on `stream`.  done[e] (int32 [N]) is
+ * the OR of the reasons:
+ *   1  the env's episode counter reaches max_episode_steps with this step (when & RP_AR_TIME_LIMIT, max_episode_steps > 0)
+ *   2  end_mask[e] != 0 (end_mask [N] uint8, may be NULL)
+ *   4  a fault, out.status & 3 (when & RP_AR_FAULT; needs out.status, else RP_ERR_ARG)
+ *   8  out.is_success (when & RP_AR_SUCCESS; needs out.is_success, else RP_ERR_ARG)
+ * For an env with done != 0: every non-NULL array of final_out gets the row rp_step wrote; the env is then reset with the draws, state record and
+ * contact-cache row rp_reset with a mask holding that env would give; out's observation arrays (and the obs_quat | achieved_goal part of out.pack)
+ * get the new episode's first observation, while out.reward, out.is_success, out.target_poses and the pack's reward / success columns keep the
+ * transition's values and out.status is the step's bits OR the reset's.  Its counter goes to 0; every other env's counter goes up by 1.
+ * rp_reset and rp_reset_to set the counters of the envs they reset to 0; rp_step leaves them alone.  The counters are not part of rp_get_state. */
+enum rp_autoreset_when { RP_AR_TIME_LIMIT = 1, RP_AR_FAULT = 2, RP_AR_SUCCESS = 4 };
+/* max_episode_steps <= 0: no time limit.  Default after rp_create: 0 / RP_AR_FAULT. */
+int rp_set_autoreset(rp_handle h, int32_t max_episode_steps, uint32_t when);
+/* per-env step counters of the current episode, int32 [N], device pointers */
+int rp_get_episode_steps(rp_handle h, int32_t* dst, void* stream);
+int rp_set_episode_steps(rp_handle h, const int32_t* src, void* stream);
+int rp_step_autoreset(rp_handle h, const float* action, const uint8_t* end_mask /* [N] or NULL */,
+                      const rp_out* out, const rp_out* final_out /* may be NULL */, int32_t* done /* [N] */, void* stream);
 
 int rp_get_timers(rp_handle h, rp_timers* t);
 /* on = number of rp_step calls to keep per-launch timings for (a ring); 0 disables */

@@ -44,6 +44,10 @@ class RpConfig(C.Structure):
 
 # rp_config_flags / rp_action_type (include/rp_playroom.h)
 CFG_GOAL_RANGE, CFG_OBJ_RANGE, CFG_ENV_RANGE, CFG_REW_THRESH, CFG_DENSE_REWARD, CFG_ACTION_TYPE, CFG_CONTACT_MARGIN, CFG_STATELESS_CONTACTS, CFG_HULL_GJK, CFG_OBB_EDGES, CFG_SPECULATIVE_LIMITS, CFG_HULL_EPA, CFG_NO_HULL_EPA = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096
+# rp_autoreset_when (include/rp_playroom.h): when rp_step_autoreset ends an episode besides end_mask
+AR_TIME_LIMIT, AR_FAULT, AR_SUCCESS = 1, 2, 4
+# the bits of rp_step_autoreset's done[] (done_reason): time limit, end_mask, fault (status & 3), is_success
+DONE_TIME_LIMIT, DONE_END_MASK, DONE_FAULT, DONE_SUCCESS = 1, 2, 4, 8
 ACTION_TYPE_CODES = {'absolute_rpy': 0, 'relative_rpy': 1, 'absolute_quat': 2, 'relative_quat': 3, 'absolute_joints': 4, 'relative_joints': 5}
 
 
@@ -73,7 +77,8 @@ class RpTimers(C.Structure):
 
 EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 'rp_reset_goal', 'rp_step', 'rp_calc_state',
            'rp_compute_reward', 'rp_compute_reward_sparse', 'rp_state_bytes', 'rp_get_state', 'rp_set_state', 'rp_get_timers', 'rp_enable_timers',
-           'rp_last_error', 'rp_version', 'rp_default_camera', 'rp_camera_from_yaw_pitch_roll', 'rp_render', 'rp_render_ex', 'rp_ray_test']
+           'rp_last_error', 'rp_version', 'rp_default_camera', 'rp_camera_from_yaw_pitch_roll', 'rp_render', 'rp_render_ex', 'rp_ray_test',
+           'rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints']
 
@@ -107,6 +112,10 @@ def load(wide=False):
     lib.rp_reset_goal.argtypes = [vp, vp, vp, vp]
     lib.rp_step.argtypes = [vp, vp, C.POINTER(RpOut), vp]
     lib.rp_calc_state.argtypes = [vp, C.POINTER(RpOut), vp]
+    lib.rp_set_autoreset.argtypes = [vp, C.c_int32, C.c_uint32]
+    lib.rp_get_episode_steps.argtypes = [vp, vp, vp]
+    lib.rp_set_episode_steps.argtypes = [vp, vp, vp]
+    lib.rp_step_autoreset.argtypes = [vp, vp, vp, C.POINTER(RpOut), C.POINTER(RpOut), vp, vp]
     lib.rp_compute_reward.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
     lib.rp_compute_reward_sparse.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
     lib.rp_state_bytes.argtypes = [vp]

@@ -5018,6 +5018,155 @@ __global__ void __launch_bounds__(64 * SOLVE_WAVES, 2) k_chain(const DevModel* _
 #endif
 }
 
+/* ------------------------------------------------------------------ rp_step_autoreset: the envs that end inside the step reset on the device, without the host.
+ * k_autoreset_mark (thread per env, after the step): the done bits, the ending envs' step rows into final_out, the episode counters, and the list of the ending envs
+ * (ballot per wave, one atomic per wave for its place in the list: the list's order is not fixed, and nothing depends on it).
+ * k_autoreset (one launch, grid = the blocks that are resident at once): every block takes envs off the list and runs each one's whole rp_reset - the same rounds as
+ * reset_split's { k_reset_sample, 100 x (k_settle_prep, k_settle_solve), k_reset_finish } with the same caps, on the env's own record, workspace row and contact-cache
+ * row - until the list is empty.  Blocks never wait for each other. */
+#define AR_BIT_TIME 1
+#define AR_BIT_MASK 2
+#define AR_BIT_FAULT 4
+#define AR_BIT_SUCCESS 8
+__global__ void __launch_bounds__(256) k_autoreset_mark(const DevModel* __restrict__ m, int N, int max_steps, unsigned when, const uint8_t* __restrict__ end_mask,
+                                                        OutPtrs out, OutPtrs fin, int* __restrict__ done, int* __restrict__ ep_steps, int* __restrict__ list,
+                                                        int* __restrict__ ctl) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
+  int bits = 0;
+  if (env < N) {
+    const int c = ep_steps[env] + 1;
+    if ((when & 1u) && max_steps > 0 && c >= max_steps) bits |= AR_BIT_TIME;       /* (when: rp_autoreset_when; the host checked the pointers bits 4 / 8 read) */
+    if (end_mask && end_mask[env]) bits |= AR_BIT_MASK;
+    if ((when & 2u) && (out.status[env] & 3)) bits |= AR_BIT_FAULT;
+    if ((when & 4u) && out.is_success[env]) bits |= AR_BIT_SUCCESS;
+    ep_steps[env] = bits ? 0 : c;
+    done[env] = bits;
+    if (bits) {      /* the step's rows of this env, before the reset overwrites them */
+      auto row = [env](float* dst, const float* src, int w) { if (dst && src) for (int k = 0; k < w; k++) dst[(size_t)env * w + k] = src[(size_t)env * w + k]; };
+      auto one = [env](int* dst, const int* src) { if (dst && src) dst[env] = src[env]; };
+      row(fin.obs_quat, out.obs_quat, m->n_obs); row(fin.achieved_goal, out.achieved_goal, m->n_ag); row(fin.desired_goal, out.desired_goal, m->n_ag);
+      row(fin.cag, out.cag, 4); row(fin.fps, out.fps, m->n_fps); row(fin.joints, out.joints, 8); row(fin.velocity, out.velocity, 6);
+      row(fin.observation, out.observation, m->n_observation); row(fin.reward, out.reward, 1); row(fin.target_poses, out.target_poses, m->n_target);
+      row(fin.pack, out.pack, m->n_obs + m->n_ag + 2);
+      one(fin.proprio, out.proprio); one(fin.is_success, out.is_success); one(fin.status, out.status);
+    }
+  }
+  const unsigned long long bal = __ballot(bits != 0);
+  int base = 0;
+  if (lane == 0 && bal != 0ull) base = atomicAdd(&ctl[0], __popcll(bal));
+  base = __shfl(base, 0);
+  if (bits) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = env;
+}
+
+/* The sample and finish phases run reset_sample_objects / reset_arm_goal_obs, one-wave bodies with block barriers inside.  Both waves of the block run them, each on its
+ * own EnvLds with the same inputs (the same branches, so the same barriers); only wave 0 (`writer`) writes to global memory. */
+struct __align__(16) AutoresetLds {
+  union { ChainLds C; EnvLds E[2]; };
+  OutPtrs out;
+  int slot[4][4];                            /* the block's slots: env (-1 = free), reset attempt, object re-samples (k_reset_finish's meta .y / .z), - */
+  int drained;                               /* the list had no env left for a free slot */
+};
+__device__ __attribute__((noinline)) void ar_sample(EnvLds* L, const DevModel* m, float* state, int env, uint64_t seed, uint32_t genv, int writer) {
+  EnvLds& E = *uniform_ptr(L);
+  m = uniform_ptr(m); state = uniform_ptr(state); env = uni(env);
+  const int lane = threadIdx.x & 63;
+  load_state(E, state, env, lane);
+  reset_sample_objects(m, E, lane, seed, genv);
+  __syncthreads();
+  if (uni(writer)) { float* r = state + (size_t)env * RP_REC_FLOATS; r[lane] = E.st[lane]; r[lane + 64] = E.st[lane + 64]; }
+}
+/* k_reset_finish on the env's own record; sl = the env's slot in LDS (env, attempt, depth), updated by the writer: env -1 once the env's reset is over */
+__device__ __attribute__((noinline)) void ar_finish(EnvLds* L, const DevModel* m, float* state, int env, uint64_t seed, uint32_t genv, const OutPtrs* o, int* sl, int writer) {
+  EnvLds& E = *uniform_ptr(L);
+  m = uniform_ptr(m); state = uniform_ptr(state); env = uni(env); writer = uni(writer); sl = uniform_ptr(sl);
+  const int lane = threadIdx.x & 63;
+  int attempt = uni(sl[1]), depth = uni(sl[2]);
+  load_state(E, state, env, lane);
+  bool over = false;
+  if (reset_objects_out_of_bounds(m, E) && depth < 8) {
+    depth++;                                       /* sample the objects again, settle again */
+  } else {
+    float tx[3];
+    const Q4 torn = {0.f, 0.f, 0.f, 1.f};
+    reset_sample_arm_target(m, E, lane, seed, genv, tx);
+    const float r = reset_arm_goal_obs(m, E, lane, seed, genv, tx, torn);
+    if (!m->dense_reward && r > -1.f && attempt + 1 < 64) { attempt++; depth = 0; }      /* already solved: the whole reset again */
+    else {
+      over = true;
+      if (writer) {      /* the new episode's observation; reward, is_success, target_poses and the pack's last two columns keep the step's values, status ORs */
+        const OutPtrs& op = *uniform_ptr(o);
+        OutPtrs ob = op;
+        ob.reward = nullptr; ob.is_success = nullptr; ob.target_poses = nullptr; ob.status = nullptr; ob.pack = nullptr;
+        write_outputs(m, E, lane, env, ob);
+        const float* s = E.out;
+        if (op.pack) {
+          const int no = m->n_obs, na = m->n_ag;
+          float* p = op.pack + (size_t)env * (no + na + 2);
+          if (lane < no) p[lane] = s[O_OBS + lane];
+          else if (lane < no + na) p[lane] = s[O_AG + lane - no];
+        }
+        if (op.status && lane == 0) op.status[env] |= __float_as_int(s[O_STATUS]);
+      }
+    }
+  }
+  __syncthreads();                                 /* (both waves have read the slot) */
+  if (writer) {
+    float* r = state + (size_t)env * RP_REC_FLOATS; r[lane] = E.st[lane]; r[lane + 64] = E.st[lane + 64];
+    if (lane == 0) { sl[1] = attempt; sl[2] = depth; if (over) sl[0] = -1; }
+  }
+}
+/* epb: envs a block settles side by side (1 .. 4: places 4 b .. 4 b + epb - 1 of pair_tab, one solve_block for all of them); pair_tab [4 * gridDim.x]; ctl[0] = the list's
+ * length (k_autoreset_mark), ctl[1] = the next entry to take (zero at launch) */
+__global__ void __launch_bounds__(64 * SOLVE_WAVES, 2) k_autoreset(const DevModel* __restrict__ m, float* state, float* ws, const int* __restrict__ list, int* ctl, int* pair_tab,
+                                                                  OutPtrs out, uint64_t seed, uint32_t env_offset, int epb, int debug_flags) {
+  __shared__ AutoresetLds L;
+  static_assert(PREP_THREADS == 64 * SOLVE_WAVES, "one block shape for both phases");
+  const int tid = threadIdx.x, wid = tid >> 6;
+  const int count = __builtin_amdgcn_readfirstlane(*(volatile int*)&ctl[0]);
+  if (count == 0) return;                                                            /* nothing ended: the blocks leave at once */
+  const int nplaces = 4 * gridDim.x;
+  if (tid < 4) { L.slot[tid][0] = -1; pair_tab[4 * blockIdx.x + tid] = -1; }
+  if (tid == 0) { L.drained = 0; L.out = out; }
+  __syncthreads();
+  for (;;) {
+    if (tid == 0 && !L.drained)
+      for (int k = 0; k < epb; k++) {
+        if (L.slot[k][0] >= 0) continue;
+        const int i = atomicAdd(&ctl[1], 1);
+        if (i >= count) { L.drained = 1; break; }
+        L.slot[k][0] = list[i]; L.slot[k][1] = 0; L.slot[k][2] = 0;
+      }
+    __syncthreads();
+    int envs[4], live = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { envs[k] = k < epb ? uni(L.slot[k][0]) : -1; live += envs[k] >= 0; }
+    if (live == 0) break;                                                            /* (block-uniform) */
+#pragma unroll 1
+    for (int k = 0; k < epb; k++)
+      if (envs[k] >= 0) { ar_sample(&L.E[wid], m, state, envs[k], seed, env_offset + (uint32_t)envs[k], wid == 0); __syncthreads(); }
+#pragma unroll 1
+    for (int i = 0; i < K_NSETTLE; i++) {
+#pragma unroll 1
+      for (int k = 0; k < epb; k++) {
+        if (envs[k] >= 0) chain_prep(&L.C.P, m, state, ws, envs[k], pair_tab, 4 * blockIdx.x + k, debug_flags & 1);
+        else if (tid == 0) pair_tab[4 * blockIdx.x + k] = -1;
+        __syncthreads();                                                             /* this env's rows and table entry are visible to the block; the LDS is free */
+      }
+      chain_solve(m, state, ws, nplaces, pair_tab, nullptr, nullptr, debug_flags | RP_DBG_NOSORT, &L.C.S, blockIdx.x);
+      __syncthreads();                                                               /* the records are written: the next substep's preparation may read them */
+    }
+#pragma unroll 1
+    for (int k = 0; k < epb; k++)
+      if (envs[k] >= 0) { ar_finish(&L.E[wid], m, state, envs[k], seed, env_offset + (uint32_t)envs[k], &L.out, L.slot[k], wid == 0); __syncthreads(); }
+  }
+}
+
+/* rp_reset / rp_reset_to: the reset envs start a new episode */
+__global__ void k_episode_zero(const uint8_t* __restrict__ mask, int* __restrict__ ep_steps, int N) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env < N && (!mask || mask[env])) ep_steps[env] = 0;
+}
+
 
 /* first pairing of a group's envs (before any load class is known): everything in the lightest class, in index order */
 __global__ void k_sort_init(int* __restrict__ cnt, int* __restrict__ slot, int env0, int ng) {

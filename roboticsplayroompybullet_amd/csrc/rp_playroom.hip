@@ -54,6 +54,10 @@ struct rp_sim {
   float* rs_state; int* rs_idx; int4* rs_meta; int* rs_count; int* rs_sort_cnt; int* rs_sort_slot; int* rs_pair; int* rs_count_host;
   int reset_rounds;        /* rounds the latest rp_reset took (rp_debug) */
   float* rc_tab; int* rc_cnt; float* rc_ee; int rc_cap; int rc_last_num;      /* rp_render / rp_ray_test: collider poses of rc_cap envs (allocated on first use) */
+  /* rp_step_autoreset: episode counters [N], the list of ending envs [N], its length and take counter [2], k_autoreset's pairing table [4 * ar_grid] */
+  int* ep_steps; int* ar_list; int* ar_ctl; int* ar_pair;
+  int ar_grid, ar_epb;     /* k_autoreset's grid (the blocks resident at once; RP_AUTORESET_BLOCKS overrides) and envs per block (RP_AUTORESET_EPB, 1 .. 4, default 1) */
+  int32_t ar_max_steps; uint32_t ar_when;      /* rp_set_autoreset */
   rp_timers timers;
   char err[256];
 };
@@ -98,15 +102,16 @@ extern "C" {
 #define RP_BUILD_ID "unversioned"
 #endif
 #ifdef RP_WIDE
-const char* rp_version(void) { return "rp_playroom 0.4 (gfx950, wide build: two-object play ids) build " RP_BUILD_ID; }
+const char* rp_version(void) { return "rp_playroom 0.5 (gfx950, wide build: two-object play ids) build " RP_BUILD_ID; }
 #else
-const char* rp_version(void) { return "rp_playroom 0.4 (gfx950) build " RP_BUILD_ID; }
+const char* rp_version(void) { return "rp_playroom 0.5 (gfx950) build " RP_BUILD_ID; }
 #endif
 
 static void destroy_handle(rp_sim* h) {        /* frees whatever a (possibly partial) handle owns; hipFree(nullptr) etc. are no-ops */
   if (!h) return;
   hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
   hipFree(h->rc_tab); hipFree(h->rc_cnt); hipFree(h->rc_ee);
+  hipFree(h->ep_steps); hipFree(h->ar_list); hipFree(h->ar_ctl); hipFree(h->ar_pair);
   hipFree(h->rs_state); hipFree(h->rs_idx); hipFree(h->rs_meta); hipFree(h->rs_count); hipFree(h->rs_sort_cnt); hipFree(h->rs_sort_slot); hipFree(h->rs_pair);
   if (h->rs_count_host) hipHostFree(h->rs_count_host);
   if (h->ev0) hipEventDestroy(h->ev0);
@@ -303,6 +308,24 @@ int rp_create(const rp_config* cfg, rp_handle* out) {
       CREATE_CHK(hipEventCreateWithFlags(&h->gjoin[i], hipEventDisableTiming));
     }
   }
+  {      /* rp_step_autoreset: counters start at 0; k_autoreset's grid is what is resident at once (it takes envs off a list, so more blocks would only wait) */
+    CREATE_CHK(hipMalloc((void**)&h->ep_steps, (size_t)N * sizeof(int)));
+    CREATE_CHK(hipMemset(h->ep_steps, 0, (size_t)N * sizeof(int)));
+    CREATE_CHK(hipMalloc((void**)&h->ar_list, (size_t)N * sizeof(int)));
+    CREATE_CHK(hipMalloc((void**)&h->ar_ctl, 2 * sizeof(int)));
+    const char* eb = getenv("RP_AUTORESET_EPB");
+    h->ar_epb = eb ? atoi(eb) : 1;
+    if (h->ar_epb < 1) h->ar_epb = 1;
+    if (h->ar_epb > 4) h->ar_epb = 4;
+    int cus = 0, per_cu = 0;
+    CREATE_CHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
+    CREATE_CHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_autoreset, 64 * SOLVE_WAVES, 0));
+    const char* ab = getenv("RP_AUTORESET_BLOCKS");
+    h->ar_grid = ab && atoi(ab) > 0 ? atoi(ab) : max(cus, 1) * max(per_cu, 1);
+    h->ar_grid = min(h->ar_grid, (N + h->ar_epb - 1) / h->ar_epb);
+    CREATE_CHK(hipMalloc((void**)&h->ar_pair, (size_t)4 * h->ar_grid * sizeof(int)));
+    h->ar_max_steps = 0; h->ar_when = RP_AR_FAULT;
+  }
   hipLaunchKernelGGL(k_init, dim3((N + 255) / 256), dim3(256), 0, 0, h->dev_model, h->state, N);
   CREATE_CHK(hipGetLastError());
   CREATE_CHK(hipDeviceSynchronize());
@@ -394,6 +417,7 @@ static int reset_impl(rp_handle h, const float* o, int32_t n_o, const uint8_t* m
   hipStream_t s = (hipStream_t)stream;
   int N = h->cfg.num_envs;
   if (h->timers_on) hipEventRecord(h->ev0, s);
+  hipLaunchKernelGGL(k_episode_zero, dim3((N + 255) / 256), dim3(256), 0, s, mask, h->ep_steps, N);      /* the reset envs start a new episode */
   if (!o && h->fused != 1) {
     int rc = reset_split(h, mask, out, s);
     if (rc != RP_OK) return rc;
@@ -574,6 +598,48 @@ int rp_step(rp_handle h, const float* action, const rp_out* out, void* stream) {
   HIPCHK(h, hipGetLastError());
   if (h->timers_on && h->fused == 1) { hipEventRecord(h->ev1, s); hipEventSynchronize(h->ev1); hipEventElapsedTime(&h->timers.last_step_ms, h->ev0, h->ev1); }
   h->timers.steps++;
+  return RP_OK;
+}
+
+int rp_set_autoreset(rp_handle h, int32_t max_episode_steps, uint32_t when) {
+  if (!h) return RP_ERR_ARG;
+  if (when & ~(uint32_t)(RP_AR_TIME_LIMIT | RP_AR_FAULT | RP_AR_SUCCESS)) { snprintf(h->err, 256, "rp_set_autoreset: unknown bits in when (0x%x)", when); return RP_ERR_ARG; }
+  h->ar_max_steps = max_episode_steps; h->ar_when = when;
+  return RP_OK;
+}
+
+int rp_get_episode_steps(rp_handle h, int32_t* dst, void* stream) {
+  if (!h || !dst) return RP_ERR_ARG;
+  DevGuard guard(h->cfg.device);
+  HIPCHK(h, hipMemcpyAsync(dst, h->ep_steps, (size_t)h->cfg.num_envs * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return RP_OK;
+}
+
+int rp_set_episode_steps(rp_handle h, const int32_t* src, void* stream) {
+  if (!h || !src) return RP_ERR_ARG;
+  DevGuard guard(h->cfg.device);
+  HIPCHK(h, hipMemcpyAsync(h->ep_steps, src, (size_t)h->cfg.num_envs * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return RP_OK;
+}
+
+/* rp_step, then on the same stream: k_autoreset_mark (done bits, final_out rows, counters, the list of ending envs) and ONE k_autoreset launch that resets the listed envs
+ * (an empty list: its blocks leave at once).  Nothing is read back; the call returns when everything is enqueued. */
+int rp_step_autoreset(rp_handle h, const float* action, const uint8_t* end_mask, const rp_out* out, const rp_out* final_out, int32_t* done, void* stream) {
+  if (!h || !action || !done) { if (h) snprintf(h->err, 256, "rp_step_autoreset: action or done is NULL"); return RP_ERR_ARG; }
+  if ((h->ar_when & RP_AR_FAULT) && (!out || !out->status)) { snprintf(h->err, 256, "rp_step_autoreset: RP_AR_FAULT reads out.status, which is NULL"); return RP_ERR_ARG; }
+  if ((h->ar_when & RP_AR_SUCCESS) && (!out || !out->is_success)) { snprintf(h->err, 256, "rp_step_autoreset: RP_AR_SUCCESS reads out.is_success, which is NULL"); return RP_ERR_ARG; }
+  int rc = rp_step(h, action, out, stream);
+  if (rc != RP_OK) return rc;
+  DevGuard guard(h->cfg.device);
+  hipStream_t s = (hipStream_t)stream;
+  const int N = h->cfg.num_envs;
+  const OutPtrs op = to_ptrs(out), fp = to_ptrs(final_out);
+  HIPCHK(h, hipMemsetAsync(h->ar_ctl, 0, 2 * sizeof(int), s));
+  hipLaunchKernelGGL(k_autoreset_mark, dim3((N + 255) / 256), dim3(256), 0, s, h->dev_model, N, (int)h->ar_max_steps, (unsigned)h->ar_when, end_mask, op, fp, done, h->ep_steps,
+                     h->ar_list, h->ar_ctl);
+  hipLaunchKernelGGL(k_autoreset, dim3(h->ar_grid), dim3(64 * SOLVE_WAVES), 0, s, h->dev_model, h->state, h->ws, (const int*)h->ar_list, h->ar_ctl, h->ar_pair, op, h->cfg.seed,
+                     (uint32_t)h->cfg.env_offset, h->ar_epb, h->debug_flags);
+  HIPCHK(h, hipGetLastError());
   return RP_OK;
 }
 

@@ -28,9 +28,14 @@ WIDE_STATE_LAYOUT = {'q': (0, 9), 'qd': (9, 18), 'free0': (18, 31), 'free1': (31
 class VecPlayEnv:
     def __init__(self, env_id, num_envs, device=0, seed=0, env_offset=0, action_type=None, goal_range_low=None, goal_range_high=None,
                  obj_lower_bound=None, obj_upper_bound=None, env_range_high=None, sparse_rew_thresh=None, sparse=True,
-                 contact_margin=None, persistent_manifolds=True, hull_gjk=True, speculative_limits=False, hull_epa=None):
-        """The keyword arguments after env_offset are the constructor kwargs of the reference's env classes that reach the
-        simulation (envList.py -> environments.py:64-67); None keeps what the id registers.  contact_margin: rp_config."""
+                 contact_margin=None, persistent_manifolds=True, hull_gjk=True, speculative_limits=False, hull_epa=None,
+                 autoreset=False, max_episode_steps=None, end_on_fault=True, end_on_success=False):
+        """The keyword arguments after env_offset up to hull_epa are the constructor kwargs of the reference's env classes that reach the
+        simulation (envList.py -> environments.py:64-67); None keeps what the id registers.  contact_margin: rp_config.
+
+        autoreset=True: step() ends episodes and resets the ended envs on the device (rp_step_autoreset), at the time limit
+        (max_episode_steps; None = the id's _max_episode_steps, 0 = none), on a fault (end_on_fault: status & 3), on success
+        (end_on_success) and where step's end_mask is set."""
         if env_id not in _lib.ENV_KINDS:
             raise NotImplementedError('env id %r is outside the hot-path scope (SURVEY.md §8)' % (env_id,))
         if not torch.cuda.is_available():
@@ -110,6 +115,18 @@ class VecPlayEnv:
         self._img = None                    # reused image buffer: obs['img'] is overwritten by the next step / reset / calc_state (clone() to keep one)
         self.sub_goal = None                # [N, dims.achieved_goal] ghosts drawn into img (visualise_sub_goal)
         self.ghost_arm = None               # [N, 8] ghost arm poses drawn into img (visualise_sub_goal's arm part, Panda ids)
+        self.autoreset = bool(autoreset)
+        if self.autoreset:
+            limit = self._max_episode_steps if max_episode_steps is None else int(max_episode_steps)
+            self.max_episode_steps = limit if limit and limit > 0 else None
+            when = _lib.AR_TIME_LIMIT | (_lib.AR_FAULT if end_on_fault else 0) | (_lib.AR_SUCCESS if end_on_success else 0)
+            _lib.check(self.lib, self.h, self.lib.rp_set_autoreset(self.h, self.max_episode_steps or 0, when), 'rp_set_autoreset')
+            # the ended envs' step rows (info['terminal_observation']) and the done reasons, owned like buf: overwritten by the next step
+            self.final = {k: f(self.dims[k]) for k in OBS_KEYS}
+            self.final['gripper_proprioception'] = torch.zeros(N, dtype=torch.int32, device=dev)
+            self.final['status'] = torch.zeros(N, dtype=torch.int32, device=dev)
+            self.final_out = _lib.RpOut(**{k: self.final[k].data_ptr() for k in self.final})
+            self._done_reason = torch.zeros(N, dtype=torch.int32, device=dev)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -167,15 +184,54 @@ class VecPlayEnv:
                        'rp_reset_to')
         return self._obs()
 
-    def step(self, action):
+    def step(self, action, end_mask=None):
+        """playEnv.step for every env.  With autoreset: the envs whose episode ended (time limit, fault, success, end_mask [N] != 0) are
+        reset inside the call, on the device - obs holds their new episode's first observation, the reward / is_success the transition's;
+        done is a bool [N] tensor, info['terminal_observation'] the ended envs' step observations (rows valid where done),
+        info['done_reason'] the int32 reasons (_lib.DONE_*), info['TimeLimit.truncated'] the envs that the time limit alone ended."""
         a = action.to(device=self.device, dtype=torch.float32).contiguous()
         assert a.shape == (self.num_envs, self.dims['action']), a.shape
+        if self.autoreset:
+            return self._step_autoreset(a, end_mask)
+        assert end_mask is None, 'end_mask needs VecPlayEnv(..., autoreset=True)'
         self._flip_pack()
         _lib.check(self.lib, self.h, self.lib.rp_step(self.h, C.c_void_p(a.data_ptr()), C.byref(self.out), self._stream()), 'rp_step')
         info = {'is_success': self.buf['is_success'], 'target_poses': self.buf['target_poses'], 'status': self.buf['status']}
         if self._done is None:      # environments.py:212: always False - one tensor for the handle's life (a fill kernel per step sat at the end of the step's chain: 8 us)
             self._done = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
         return self._obs(), self.buf['reward'], self._done, info
+
+    def _step_autoreset(self, a, end_mask):
+        mp = None
+        if end_mask is not None:
+            end_mask = end_mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            assert end_mask.shape == (self.num_envs,), end_mask.shape
+            mp = C.c_void_p(end_mask.data_ptr())
+        self._flip_pack()
+        _lib.check(self.lib, self.h, self.lib.rp_step_autoreset(self.h, C.c_void_p(a.data_ptr()), mp, C.byref(self.out), C.byref(self.final_out),
+                                                                C.c_void_p(self._done_reason.data_ptr()), self._stream()), 'rp_step_autoreset')
+        reason = self._done_reason
+        info = {'is_success': self.buf['is_success'], 'target_poses': self.buf['target_poses'], 'status': self.buf['status'],
+                'terminal_observation': {k: self.final[k] for k in OBS_KEYS + ('gripper_proprioception',)},
+                'terminal_status': self.final['status'],
+                'TimeLimit.truncated': reason == _lib.DONE_TIME_LIMIT,      # gym 0.21: the time limit and nothing else ended the episode
+                'done_reason': reason}
+        return self._obs(), self.buf['reward'], reason != 0, info
+
+    @property
+    def episode_steps(self):
+        """int32 [N]: steps of every env's current episode (rp_step_autoreset counts them; reset() sets the reset envs' to 0)"""
+        t = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib, self.h, self.lib.rp_get_episode_steps(self.h, C.c_void_p(t.data_ptr()), self._stream()), 'rp_get_episode_steps')
+        return t
+
+    @episode_steps.setter
+    def episode_steps(self, steps):
+        """e.g. env.episode_steps = torch.arange(N) % limit: staggered time limits"""
+        t = torch.as_tensor(steps).to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        assert t.shape == (self.num_envs,), t.shape
+        _lib.check(self.lib, self.h, self.lib.rp_set_episode_steps(self.h, C.c_void_p(t.data_ptr()), self._stream()), 'rp_set_episode_steps')
+        self._ep_src = t      # (kept until the next set: the copy reads it when the stream gets there)
 
     def calc_state(self):
         self._flip_pack()
