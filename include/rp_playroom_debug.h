@@ -31,6 +31,9 @@ int rp_debug_row_counts(rp_handle h, int32_t* host_buf);
 int rp_debug_ghost_joints(rp_handle h, float* host_buf, int32_t num_envs);
 /* rounds the most recent rp_reset took */
 int rp_debug_reset_rounds(rp_handle h);
+/* k_autoreset's launch shape, fixed at rp_create: *grid = its blocks (the blocks resident at once, or RP_AUTORESET_BLOCKS; never more than
+ * ceil(num_envs / epb)), *epb = the envs a block settles side by side (RP_AUTORESET_EPB, 1 .. 4) */
+int rp_debug_autoreset_shape(rp_handle h, int32_t* grid, int32_t* epb);
 /* PROFILING BUILDS ONLY (tools/build_profiling_libs.sh: -DRP_CLOCKS=1|2, -DRP_PROLOGUE_CLOCKS, -DRP_CHAIN_CLOCKS).  The shipped library exports none of these and
  * tests/test_abi.py does not expect them; such a build also exports, for the tools that load it through RP_PLAYROOM_LIB:
  *     rp_debug_clocks(rp_handle, uint64_t* host_buf, int32_t nwaves)              s_memtime marks per wave of k_solve2 (RP_CLOCKS=1) / per block of k_prep2 (=2)

@@ -80,7 +80,8 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_last_error', 'rp_version', 'rp_default_camera', 'rp_camera_from_yaw_pitch_roll', 'rp_render', 'rp_render_ex', 'rp_ray_test',
            'rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset']
 # include/rp_playroom_debug.h: test / tuning hooks
-DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints']
+DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
+                 'rp_debug_autoreset_shape']
 
 _lib = None
 _libs = {}
@@ -139,6 +140,7 @@ def load(wide=False):
     lib.rp_debug_ghost_joints.argtypes = [vp, C.c_void_p, C.c_int32]
     lib.rp_debug_row_counts.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.rp_debug_reset_rounds.argtypes = [vp]
+    lib.rp_debug_autoreset_shape.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     _libs[path] = lib
     if not wide:
         _lib = lib

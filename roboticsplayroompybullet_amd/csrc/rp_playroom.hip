@@ -824,6 +824,13 @@ const char* rp_last_error(rp_handle h) { return h ? h->err : g_err; }
 
 int rp_debug_reset_rounds(rp_handle h) { return h ? h->reset_rounds : RP_ERR_ARG; }
 
+/* test hook: k_autoreset's launch shape as rp_create fixed it - grid (blocks) and envs per block (RP_AUTORESET_BLOCKS / RP_AUTORESET_EPB) */
+int rp_debug_autoreset_shape(rp_handle h, int32_t* grid, int32_t* epb) {
+  if (!h || !grid || !epb) return RP_ERR_ARG;
+  *grid = h->ar_grid; *epb = h->ar_epb;
+  return RP_OK;
+}
+
 /* test hooks (include/rp_playroom_debug.h): one substep on every env, intermediates of env `env` into host buf[4096] */
 int rp_debug_substep(rp_handle h, int32_t env, float* host_buf) {
   if (!h || !host_buf) return RP_ERR_ARG;

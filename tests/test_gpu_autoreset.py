@@ -4,8 +4,13 @@ The yardstick is the host-driven path the library already has: a twin handle wit
 rp_reset(mask) with the envs that should have ended.  The counter-keyed RNG makes a reset's draws independent of which other envs reset with it,
 so the two must agree bit for bit.
 """
+import collections
+import ctypes as C
+
 import numpy as np
 import pytest
+
+from reset_draws import DRAWS, RNG_COL, decode
 
 torch = pytest.importorskip('torch')
 
@@ -44,37 +49,38 @@ def make(gid, n, seed, **kw):
     return VecPlayEnv(gid, n, seed=seed, **kw)
 
 
-@pytest.mark.parametrize('gid', IDS)
-def test_autoreset_equals_step_then_masked_reset_bitwise(gid):
-    """handle A: rp_step_autoreset with a time limit of 4 (counters staggered e % 4), a random 5 % end_mask and the fault rule; twin B: rp_step, rows
-    kept, rp_reset(mask of the envs that ended).  A's observations, the pack's observation part and every state row (record + contact cache) equal B's
-    after its reset; A's reward / is_success / target_poses and the pack's last two columns equal B's step rows; A's status = B's step status | its
-    reset status; terminal_observation = B's step rows; done = the expected mask; the counters follow."""
-    n, steps, seed = 256, 20, 11
-    A = make(gid, n, seed, autoreset=True, max_episode_steps=4)
-    B = make(gid, n, seed)
-    A.reset(); B.reset()
+def compare_with_twin(A, B, steps, seed, stagger, full_ends=()):
+    """A: rp_step_autoreset (time limit = stagger, counters staggered e % stagger, a random 5 % end_mask - all ones in the steps `full_ends` - and the fault
+    rule); twin B: rp_step, rows kept, rp_reset(mask of the envs that ended).  A's observations, the pack's observation part and every state row (record +
+    contact cache) equal B's after its reset; A's reward / is_success / target_poses and the pack's last two columns equal B's step rows; A's status = B's
+    step status | its reset status; terminal_observation = B's step rows; done = the expected mask; the counters follow.  Returns the ends of every step
+    and the RNG draws (ST_RNG after - before B's reset) of every env that ended; an env that did not end drew nothing."""
+    n = A.num_envs
     dev = A.device
     e = torch.arange(n, device=dev, dtype=torch.int32)
-    A.episode_steps = e % 4
-    cnt = (e % 4).clone()
+    A.episode_steps = e % stagger
+    cnt = (e % stagger).clone()
     acts = actions(A, steps, seed)
     masks = end_masks(n, steps, seed + 1, dev)
+    for t in full_ends:
+        masks[t] = torch.ones(n, device=dev, dtype=torch.uint8)
     no, na = A.dims['obs_quat'], A.dims['achieved_goal']
-    ended = 0
+    col = RNG_COL[A.wide]
+    ends, draws = [], []
     for t in range(steps):
         oa, ra, da, ia = A.step(acts[t], end_mask=masks[t])
         B.step(acts[t])
         kept = {k: B.buf[k].clone() for k in OBS + ('reward', 'is_success', 'target_poses', 'status')}
         kept_pack = B.pack.clone()
+        rng0 = B.get_state()[:, col].contiguous().view(torch.int32)
         c1 = cnt + 1
-        reason = (c1 >= 4).int() | (masks[t] != 0).int() * 2 | ((kept['status'] & 3) != 0).int() * 4
+        reason = (c1 >= stagger).int() | (masks[t] != 0).int() * 2 | ((kept['status'] & 3) != 0).int() * 4
         mask = reason != 0
         cnt = torch.where(mask, torch.zeros_like(c1), c1)
         if bool(mask.any()):
             B.reset(mask=mask)
         torch.cuda.synchronize()
-        ended += int(mask.sum())
+        ends.append(int(mask.sum()))
         assert torch.equal(da, mask), t
         assert torch.equal(ia['done_reason'], reason), t
         assert torch.equal(ia['TimeLimit.truncated'], reason == 1), t
@@ -86,13 +92,91 @@ def test_autoreset_equals_step_then_masked_reset_bitwise(gid):
         assert torch.equal(ia['is_success'], kept['is_success']), t
         assert torch.equal(ia['target_poses'], kept['target_poses']), t
         assert torch.equal(ia['status'], kept['status'] | B.buf['status']), t
-        assert torch.equal(A.get_state(), B.get_state()), t
+        sb = B.get_state()
+        assert torch.equal(A.get_state(), sb), t
         term = ia['terminal_observation']
         for k in OBS:
             assert torch.equal(term[k][mask], kept[k][mask]), (t, k)
         assert torch.equal(ia['terminal_status'][mask], kept['status'][mask]), t
         assert torch.equal(A.episode_steps, cnt), t
+        used = sb[:, col].contiguous().view(torch.int32) - rng0
+        assert not bool(used[~mask].any()), t
+        draws.append(used[mask].cpu())
+    return ends, torch.cat(draws).tolist()
+
+
+@pytest.mark.parametrize('gid', IDS)
+def test_autoreset_equals_step_then_masked_reset_bitwise(gid):
+    """handle A: rp_step_autoreset with a time limit of 4 (counters staggered e % 4), a random 5 % end_mask and the fault rule; twin B: rp_step, rows
+    kept, rp_reset(mask of the envs that ended).  A's observations, the pack's observation part and every state row (record + contact cache) equal B's
+    after its reset; A's reward / is_success / target_poses and the pack's last two columns equal B's step rows; A's status = B's step status | its
+    reset status; terminal_observation = B's step rows; done = the expected mask; the counters follow."""
+    n, steps, seed = 256, 20, 11
+    A = make(gid, n, seed, autoreset=True, max_episode_steps=4)
+    B = make(gid, n, seed)
+    A.reset(); B.reset()
+    ends, _ = compare_with_twin(A, B, steps, seed, 4)
+    ended = sum(ends)
     assert ended > n * steps // 5, ended           # the time limit alone ends a quarter of the envs every step
+
+
+def autoreset_shape(env):
+    grid, epb = C.c_int32(), C.c_int32()
+    assert env.lib.rp_debug_autoreset_shape(env.h, C.byref(grid), C.byref(epb)) == 0
+    return grid.value, epb.value
+
+
+SHAPES = ((None, 2), (None, 4), (1, 1), (1, 4), (3, 3), (7, 2))
+N_SMALL, N_LARGE = 100, 4196
+
+
+@pytest.mark.parametrize('blocks,epb', SHAPES, ids=['blocks%s-epb%d' % (b or 'default', e) for b, e in SHAPES])
+@pytest.mark.parametrize('gid', tuple(DRAWS))
+def test_shared_blocks_refilled_slots_and_retries_bitwise(gid, blocks, epb, monkeypatch):
+    """k_autoreset off its one-env-per-block path: RP_AUTORESET_BLOCKS / RP_AUTORESET_EPB set for handle A only, the same comparison with twin B as
+    test_autoreset_equals_step_then_masked_reset_bitwise, and two steps in which every env ends.
+
+    There the ends outnumber the grid's slots (grid x epb, read back with rp_debug_autoreset_shape), so slots are refilled from the list after their env
+    is done.  With the default grid that takes more envs than the blocks resident at once hold (MI355X: 1024 blocks): N = 4196, otherwise N = 100; both
+    leave k_autoreset_mark's last wave partial.  Every ended env's reset is decoded from its RNG draws (tests/reset_draws.py) into extra attempts (a
+    solved sparse goal: the whole reset again) and object re-samples (depth: settled out of bounds); both retry branches must have been compared bit
+    for bit.  Measured on the MI355X, seed 11 (the same in every shape: the draws do not depend on the launch shape), envs with attempt > 0 / with
+    depth > 0 among the ends:
+        N = 4196 (8828 ends)   U: 2856 / 0      P: 5 / 190     W: 5086 / 323
+        N = 100  (212 ends)    U: 72 / 0        P: 0 / 2       W: 108 / 4
+    So the attempt branch is asserted for U and W in every shape and for P at N = 4196 (epb 2, 4); the depth branch for P and W in every shape.  U
+    settled no object out of bounds in 9040 device resets (the oracle: none in 300), so U's depth branch is left to
+    test_refilled_slot_starts_its_own_resample_count."""
+    big = blocks is None
+    n = N_LARGE if big else N_SMALL
+    steps, seed, stagger, full_ends = (4, 11, 4, (0, 2)) if big else (5, 11, 4, (0, 3))
+    monkeypatch.delenv('RP_AUTORESET_BLOCKS', raising=False)
+    monkeypatch.delenv('RP_AUTORESET_EPB', raising=False)
+    B = make(gid, n, seed)
+    if blocks is not None:
+        monkeypatch.setenv('RP_AUTORESET_BLOCKS', str(blocks))
+    monkeypatch.setenv('RP_AUTORESET_EPB', str(epb))
+    A = make(gid, n, seed, autoreset=True, max_episode_steps=stagger)
+    grid_b, epb_b = autoreset_shape(B)
+    assert epb_b == 1 and 1 <= grid_b <= n, (grid_b, epb_b)
+    grid, got_epb = autoreset_shape(A)
+    assert got_epb == epb and (blocks is None or grid == blocks), (grid, got_epb)
+    A.reset(); B.reset()
+    ends, draws = compare_with_twin(A, B, steps, seed, stagger, full_ends)
+    per_attempt, per_resample = DRAWS[gid]
+    decoded = [decode(d, per_attempt, per_resample) for d in draws]
+    assert None not in decoded, sorted(set(d for d, x in zip(draws, decoded) if x is None))
+    retried = sum(a > 0 for a, _ in decoded)
+    resampled = sum(s > 0 for _, s in decoded)
+    beyond = sum(max(0, x - grid * epb) for x in ends)
+    print('%s blocks=%s: grid %d, epb %d, N %d, ends %d (per step %s), ends beyond grid x epb %d, envs with attempt > 0: %d, with depth > 0: %d, '
+          'draws %s' % (gid, blocks, grid, epb, n, sum(ends), ends, beyond, retried, resampled, sorted(collections.Counter(draws).items())))
+    for t in full_ends:
+        assert ends[t] == n and ends[t] > grid * epb, (t, ends[t], grid, epb)
+    if gid != 'pandaPick-v0' or big:
+        assert retried > 0, retried
+    if gid != 'UR5PlayAbsRPY1Obj-v0':
+        assert resampled > 0, resampled
 
 
 def test_no_ends_equals_rp_step_bitwise():
@@ -238,3 +322,30 @@ def test_step_returns_before_the_gpu_is_done():
     torch.cuda.synchronize()
     assert busy
     assert bool(done.all())
+
+
+@pytest.mark.parametrize('blocks,epb', ((3, 3), (7, 2)), ids=('blocks3-epb3', 'blocks7-epb2'))
+@pytest.mark.parametrize('gid', tuple(DRAWS))
+def test_refilled_slot_starts_its_own_resample_count(gid, blocks, epb, monkeypatch):
+    """every object sample settles out of bounds (env_range_high's z below the table), so every attempt of every reset runs into the depth cap: 9
+    samples, per_attempt + 8 x per_resample draws.  A slot refilled after such an env must start the next env at depth 0 - one that kept the old slot's
+    depth 8 would sample once and differ from twin B (same ranges) and from the draw count.  Seed 11, N = 100, grid x epb = 9 / 14, two steps in which
+    all envs end, one with the time limit's quarter.  Measured (draws: count): U 35: 141, 70: 41, 105: 16, 140: 4; P 33: 202; W 65: 82, 130: 50, ...
+    up to 780 (12 attempts)."""
+    n, steps, seed, stagger = 100, 3, 11, 4
+    hi = [1.0, 1.0, -1.0]
+    monkeypatch.delenv('RP_AUTORESET_BLOCKS', raising=False)
+    monkeypatch.delenv('RP_AUTORESET_EPB', raising=False)
+    B = make(gid, n, seed, env_range_high=hi)
+    monkeypatch.setenv('RP_AUTORESET_BLOCKS', str(blocks))
+    monkeypatch.setenv('RP_AUTORESET_EPB', str(epb))
+    A = make(gid, n, seed, env_range_high=hi, autoreset=True, max_episode_steps=stagger)
+    grid, got_epb = autoreset_shape(A)
+    assert (grid, got_epb) == (blocks, epb)
+    A.reset(); B.reset()
+    ends, draws = compare_with_twin(A, B, steps, seed, stagger, (0, 2))
+    per_attempt, per_resample = DRAWS[gid]
+    capped = per_attempt + 8 * per_resample
+    print('%s blocks=%d epb=%d: ends %s, draws %s' % (gid, blocks, epb, ends, sorted(collections.Counter(draws).items())))
+    assert ends[0] == ends[2] == n and n > grid * epb
+    assert all(d > 0 and d % capped == 0 for d in draws), sorted(set(draws))
