@@ -265,6 +265,18 @@ int rp_get_episode_steps(rp_handle h, int32_t* dst, void* stream);
 int rp_set_episode_steps(rp_handle h, const int32_t* src, void* stream);
 int rp_step_autoreset(rp_handle h, const float* action, const uint8_t* end_mask /* [N] or NULL */,
                       const rp_out* out, const rp_out* final_out /* may be NULL */, int32_t* done /* [N] */, void* stream);
+/* A table of `rows` start vectors o [rows, n_o] (device pointer, the layout rp_reset_to reads; an obs_quat row of the same id is one), copied into
+ * library memory on `stream`.  While a table is set, rp_step_autoreset resets every ended env with rp_reset_to semantics from one table row instead of
+ * settling: the ended env e gets row (cursor + rank(e)) mod rows, rank(e) = the ended envs with a smaller index in this call, and the cursor then
+ * moves on by the number of ends, mod rows.  Everything else follows the rules above (the state record, contact-cache row and outputs are what
+ * rp_step followed by rp_reset_to with those rows and a mask of the ended envs would leave, under the autoreset output rules).  rows = 0 (o may be
+ * NULL) removes the table: autoreset settles again.  Sets the row cursor to 0.  Synchronises the device before it frees a replaced table; rp_reset and
+ * rp_reset_to do not move the cursor, and neither the table nor the cursor is part of rp_get_state.  n_o below what rp_reset_to reads for this id,
+ * or rows < 0: RP_ERR_ARG. */
+int rp_set_reset_table(rp_handle h, const float* o, int32_t rows, int32_t n_o, void* stream);
+/* int32 [N] device pointer: the table row each env's latest rp_step_autoreset started its new episode from; -1 where the env did not end, or ended
+ * while no table was set */
+int rp_get_reset_rows(rp_handle h, int32_t* dst, void* stream);
 
 int rp_get_timers(rp_handle h, rp_timers* t);
 /* on = number of rp_step calls to keep per-launch timings for (a ring); 0 disables */

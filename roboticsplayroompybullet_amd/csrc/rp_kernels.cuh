@@ -3159,6 +3159,38 @@ __device__ float reset_arm_goal_obs(const DevModel* m, EnvLds& L, int lane, uint
   return r;
 }
 
+/* playEnv.reset(o) (environments.py:173-187, 519-525, 542-556, 575-590) on the record in L, repeated while the drawn goal is already solved (64 attempts at
+ * most): drawer / scene joints to their defaults, the object block read from o[11:18] (use_orientation) or o[7:10], the arm's IK target from o[0:3]
+ * (+ o[3:7] / o[6:10]); no settling.  k_reset (rp_reset_to) and k_autoreset_to (a reset table) run it. */
+__device__ void reset_to_obs(const DevModel* m, EnvLds& L, int lane, const float* __restrict__ o, uint64_t seed, uint32_t genv) {
+  float r = 0.f;
+  for (int attempt = 0; attempt < 64 && r > -1.f; attempt++) {
+    float tx[3];
+    Q4 torn = {0.f, 0.f, 0.f, 1.f};
+    if (lane == 0) {
+      if (m->play) {
+        float* d = &L.st[ST_FREE + 13 * m->drawer_free];
+        for (int k = 0; k < 3; k++) d[k] = m->free_pos0[m->drawer_free][k];
+        for (int k = 0; k < 4; k++) d[3 + k] = m->free_quat0[m->drawer_free][k];
+        for (int k = 7; k < 13; k++) d[k] = 0.f;
+        for (int k = 0; k < m->n_j1; k++) { L.st[ST_JQ + k] = 0.f; L.st[ST_JQD + k] = 0.f; }
+      }
+      int index = m->use_orientation ? 11 : 7, inc = m->use_orientation ? 10 : 6;
+      for (int b = 0; b < m->num_objects; b++) {
+        float* f = &L.st[ST_FREE + 13 * b];
+        for (int k = 0; k < 3; k++) f[k] = o[index + k];
+        if (m->use_orientation) for (int k = 0; k < 4; k++) f[3 + k] = o[index + 3 + k];
+        else { f[3] = 0.f; f[4] = 0.f; f[5] = 0.f; f[6] = 1.f; }
+        for (int k = 7; k < 13; k++) f[k] = 0.f;
+        index += inc;
+      }
+    }
+    tx[0] = o[0]; tx[1] = o[1]; tx[2] = o[2];
+    if (m->use_orientation) { int q0 = m->return_velocity ? 6 : 3; torn.x = o[q0]; torn.y = o[q0 + 1]; torn.z = o[q0 + 2]; torn.w = o[q0 + 3]; }
+    r = reset_arm_goal_obs(m, L, lane, seed, genv, tx, torn);
+  }
+}
+
 /* playEnv.reset(o=None) and reset(o) (environments.py:173-187, 519-603) in one kernel, one wave per env, the settle substeps
  * through the fused substep().  rp_reset_to uses it (no settling there), and rp_reset when the fused path is selected; the
  * default rp_reset runs the same sequence through the split pipeline (k_reset_* below). */
@@ -3170,43 +3202,21 @@ __global__ void __launch_bounds__(64, RP_WAVES_PER_EU) k_reset(const DevModel* _
   if (mask && !mask[env]) return;
   uint32_t genv = env_offset + (uint32_t)env;
   load_state(L, state, env, lane);
-  float r = 0.f;
-  for (int attempt = 0; attempt < 64 && r > -1.f; attempt++) {
-    float tx[3];
-    Q4 torn = {0.f, 0.f, 0.f, 1.f};
-    if (obs_o) {
-      /* reset(o) (environments.py:519-525, 542-556, 575-590): drawer / scene joints to their defaults, the object block read
-       * from o[11:18] (use_orientation) or o[7:10], the arm's IK target from o[0:3] (+ o[3:7] / o[6:10]); no settling */
-      const float* o = obs_o + (size_t)env * n_o;
-      if (lane == 0) {
-        if (m->play) {
-          float* d = &L.st[ST_FREE + 13 * m->drawer_free];
-          for (int k = 0; k < 3; k++) d[k] = m->free_pos0[m->drawer_free][k];
-          for (int k = 0; k < 4; k++) d[3 + k] = m->free_quat0[m->drawer_free][k];
-          for (int k = 7; k < 13; k++) d[k] = 0.f;
-          for (int k = 0; k < m->n_j1; k++) { L.st[ST_JQ + k] = 0.f; L.st[ST_JQD + k] = 0.f; }
-        }
-        int index = m->use_orientation ? 11 : 7, inc = m->use_orientation ? 10 : 6;
-        for (int b = 0; b < m->num_objects; b++) {
-          float* f = &L.st[ST_FREE + 13 * b];
-          for (int k = 0; k < 3; k++) f[k] = o[index + k];
-          if (m->use_orientation) for (int k = 0; k < 4; k++) f[3 + k] = o[index + 3 + k];
-          else { f[3] = 0.f; f[4] = 0.f; f[5] = 0.f; f[6] = 1.f; }
-          for (int k = 7; k < 13; k++) f[k] = 0.f;
-          index += inc;
-        }
-      }
-      tx[0] = o[0]; tx[1] = o[1]; tx[2] = o[2];
-      if (m->use_orientation) { int q0 = m->return_velocity ? 6 : 3; torn.x = o[q0]; torn.y = o[q0 + 1]; torn.z = o[q0 + 2]; torn.w = o[q0 + 3]; }
-    } else {
+  if (obs_o) {
+    reset_to_obs(m, L, lane, obs_o + (size_t)env * n_o, seed, genv);
+  } else {
+    float r = 0.f;
+    for (int attempt = 0; attempt < 64 && r > -1.f; attempt++) {
+      float tx[3];
+      const Q4 torn = {0.f, 0.f, 0.f, 1.f};
       for (int depth = 0; depth < 9; depth++) {
         reset_sample_objects(m, L, lane, seed, genv);
         for (int i = 0; i < K_NSETTLE; i++) substep(m, L, lane, env);
         if (!reset_objects_out_of_bounds(m, L)) break;
       }
       reset_sample_arm_target(m, L, lane, seed, genv, tx);
+      r = reset_arm_goal_obs(m, L, lane, seed, genv, tx, torn);
     }
-    r = reset_arm_goal_obs(m, L, lane, seed, genv, tx, torn);
   }
   write_outputs(m, L, lane, env, out);
   store_state(L, state, env, lane);
@@ -5023,17 +5033,20 @@ __global__ void __launch_bounds__(64 * SOLVE_WAVES, 2) k_chain(const DevModel* _
  * (ballot per wave, one atomic per wave for its place in the list: the list's order is not fixed, and nothing depends on it).
  * k_autoreset (one launch, grid = the blocks that are resident at once): every block takes envs off the list and runs each one's whole rp_reset - the same rounds as
  * reset_split's { k_reset_sample, 100 x (k_settle_prep, k_settle_solve), k_reset_finish } with the same caps, on the env's own record, workspace row and contact-cache
- * row - until the list is empty.  Blocks never wait for each other. */
+ * row - until the list is empty.  Blocks never wait for each other.
+ * With a reset table (rp_set_reset_table) k_autoreset_rows and k_autoreset_to take k_autoreset's place: the ended envs restart from table rows with rp_reset_to's
+ * semantics, no settling (below k_autoreset). */
 #define AR_BIT_TIME 1
 #define AR_BIT_MASK 2
 #define AR_BIT_FAULT 4
 #define AR_BIT_SUCCESS 8
 __global__ void __launch_bounds__(256) k_autoreset_mark(const DevModel* __restrict__ m, int N, int max_steps, unsigned when, const uint8_t* __restrict__ end_mask,
                                                         OutPtrs out, OutPtrs fin, int* __restrict__ done, int* __restrict__ ep_steps, int* __restrict__ list,
-                                                        int* __restrict__ ctl) {
+                                                        int* __restrict__ ctl, int* __restrict__ reset_rows, unsigned long long* __restrict__ wave_bal) {
   const int env = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
   int bits = 0;
   if (env < N) {
+    reset_rows[env] = -1;                          /* (k_autoreset_to sets the rows of the envs it resets from a table) */
     const int c = ep_steps[env] + 1;
     if ((when & 1u) && max_steps > 0 && c >= max_steps) bits |= AR_BIT_TIME;       /* (when: rp_autoreset_when; the host checked the pointers bits 4 / 8 read) */
     if (end_mask && end_mask[env]) bits |= AR_BIT_MASK;
@@ -5056,6 +5069,7 @@ __global__ void __launch_bounds__(256) k_autoreset_mark(const DevModel* __restri
   if (lane == 0 && bal != 0ull) base = atomicAdd(&ctl[0], __popcll(bal));
   base = __shfl(base, 0);
   if (bits) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = env;
+  if (wave_bal && lane == 0) wave_bal[env >> 6] = bal;      /* a reset table: each wave's ends, which k_autoreset_rows ranks in env order */
 }
 
 /* The sample and finish phases run reset_sample_objects / reset_arm_goal_obs, one-wave bodies with block barriers inside.  Both waves of the block run them, each on its
@@ -5066,6 +5080,20 @@ struct __align__(16) AutoresetLds {
   int slot[4][4];                            /* the block's slots: env (-1 = free), reset attempt, object re-samples (k_reset_finish's meta .y / .z), - */
   int drained;                               /* the list had no env left for a free slot */
 };
+/* the new episode's first observation under rp_step_autoreset's rules: reward, is_success, target_poses and the pack's last two columns keep the step's values, status ORs */
+__device__ __forceinline__ void ar_write_outputs(const DevModel* m, const EnvLds& E, int lane, int env, const OutPtrs& op) {
+  OutPtrs ob = op;
+  ob.reward = nullptr; ob.is_success = nullptr; ob.target_poses = nullptr; ob.status = nullptr; ob.pack = nullptr;
+  write_outputs(m, E, lane, env, ob);
+  const float* s = E.out;
+  if (op.pack) {
+    const int no = m->n_obs, na = m->n_ag;
+    float* p = op.pack + (size_t)env * (no + na + 2);
+    if (lane < no) p[lane] = s[O_OBS + lane];
+    else if (lane < no + na) p[lane] = s[O_AG + lane - no];
+  }
+  if (op.status && lane == 0) op.status[env] |= __float_as_int(s[O_STATUS]);
+}
 __device__ __attribute__((noinline)) void ar_sample(EnvLds* L, const DevModel* m, float* state, int env, uint64_t seed, uint32_t genv, int writer) {
   EnvLds& E = *uniform_ptr(L);
   m = uniform_ptr(m); state = uniform_ptr(state); env = uni(env);
@@ -5093,20 +5121,7 @@ __device__ __attribute__((noinline)) void ar_finish(EnvLds* L, const DevModel* m
     if (!m->dense_reward && r > -1.f && attempt + 1 < 64) { attempt++; depth = 0; }      /* already solved: the whole reset again */
     else {
       over = true;
-      if (writer) {      /* the new episode's observation; reward, is_success, target_poses and the pack's last two columns keep the step's values, status ORs */
-        const OutPtrs& op = *uniform_ptr(o);
-        OutPtrs ob = op;
-        ob.reward = nullptr; ob.is_success = nullptr; ob.target_poses = nullptr; ob.status = nullptr; ob.pack = nullptr;
-        write_outputs(m, E, lane, env, ob);
-        const float* s = E.out;
-        if (op.pack) {
-          const int no = m->n_obs, na = m->n_ag;
-          float* p = op.pack + (size_t)env * (no + na + 2);
-          if (lane < no) p[lane] = s[O_OBS + lane];
-          else if (lane < no + na) p[lane] = s[O_AG + lane - no];
-        }
-        if (op.status && lane == 0) op.status[env] |= __float_as_int(s[O_STATUS]);
-      }
+      if (writer) ar_write_outputs(m, E, lane, env, *uniform_ptr(o));      /* the new episode's observation */
     }
   }
   __syncthreads();                                 /* (both waves have read the slot) */
@@ -5158,6 +5173,53 @@ __global__ void __launch_bounds__(64 * SOLVE_WAVES, 2) k_autoreset(const DevMode
 #pragma unroll 1
     for (int k = 0; k < epb; k++)
       if (envs[k] >= 0) { ar_finish(&L.E[wid], m, state, envs[k], seed, env_offset + (uint32_t)envs[k], &L.out, L.slot[k], wid == 0); __syncthreads(); }
+  }
+}
+
+/* ---- rp_step_autoreset with a reset table: every ended env e restarts with rp_reset_to's semantics from row (cursor + rank(e)) mod rows, rank(e) = the ended envs
+ * below e in this call.  The list's order is not fixed (one atomic per wave), so the rank comes from the waves' ballots, which k_autoreset_mark keeps in env order.
+ * k_autoreset_rows (one block): each wave's first row, (cursor + the ends of the waves before it) mod rows, and the cursor moves on by all the ends.  At N = 4 M
+ * that is 65 536 ballots, 64 per thread. */
+__global__ void __launch_bounds__(1024) k_autoreset_rows(const unsigned long long* __restrict__ wave_bal, int nw, int* __restrict__ wave_row, int* cursor, int rows) {
+  __shared__ int part[16];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const long long c0 = *cursor;
+  const int per = (nw + 1023) / 1024, w0 = min(tid * per, nw), w1 = min(w0 + per, nw);
+  int own = 0;
+  for (int w = w0; w < w1; w++) own += __popcll(wave_bal[w]);
+  int inc = own;                                   /* inclusive scan over the wave's threads, then over the 16 waves */
+  for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(inc, d); if (lane >= d) inc += v; }
+  if (lane == 63) part[wid] = inc;
+  __syncthreads();
+  if (wid == 0) {
+    int v = lane < 16 ? part[lane] : 0;
+    for (int d = 1; d < 16; d <<= 1) { const int u = __shfl_up(v, d); if (lane >= d) v += u; }
+    if (lane < 16) part[lane] = v;
+  }
+  __syncthreads();
+  long long acc = c0 + (wid > 0 ? part[wid - 1] : 0) + inc - own;
+  for (int w = w0; w < w1; w++) { wave_row[w] = (int)(acc % rows); acc += __popcll(wave_bal[w]); }
+  if (tid == 0) *cursor = (int)((c0 + part[15]) % rows);      /* (every thread read the cursor before the first barrier) */
+}
+
+/* One wave per env, grid = the waves that are resident at once (rp_create), striding over the list: an empty list costs one empty launch.  Per env: the row, then
+ * k_reset's reset(o) body on the env's record (reset_to_obs) - its contact-cache row is left as rp_reset_to leaves it - and the outputs under the autoreset rules. */
+__global__ void __launch_bounds__(64, RP_WAVES_PER_EU) k_autoreset_to(const DevModel* __restrict__ m, float* __restrict__ state, const int* __restrict__ list,
+                                                                     const int* ctl, const unsigned long long* __restrict__ wave_bal, const int* __restrict__ wave_row,
+                                                                     const float* __restrict__ table, int rows, int n_o, int* __restrict__ reset_rows, OutPtrs out,
+                                                                     uint64_t seed, uint32_t env_offset) {
+  __shared__ EnvLds L;
+  const int lane = threadIdx.x;
+  const int count = __builtin_amdgcn_readfirstlane(*(volatile const int*)&ctl[0]);
+  for (int i = blockIdx.x; i < count; i += gridDim.x) {
+    const int env = uni(list[i]);
+    const unsigned long long below = wave_bal[env >> 6] & ((1ull << (env & 63)) - 1ull);
+    const int row = uni((int)(((unsigned long long)wave_row[env >> 6] + (unsigned long long)__popcll(below)) % (unsigned long long)rows));
+    load_state(L, state, env, lane);
+    reset_to_obs(m, L, lane, table + (size_t)row * n_o, seed, env_offset + (uint32_t)env);
+    ar_write_outputs(m, L, lane, env, out);
+    store_state(L, state, env, lane);
+    if (lane == 0) reset_rows[env] = row;
   }
 }
 

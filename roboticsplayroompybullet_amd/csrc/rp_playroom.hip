@@ -58,6 +58,9 @@ struct rp_sim {
   int* ep_steps; int* ar_list; int* ar_ctl; int* ar_pair;
   int ar_grid, ar_epb;     /* k_autoreset's grid (the blocks resident at once; RP_AUTORESET_BLOCKS overrides) and envs per block (RP_AUTORESET_EPB, 1 .. 4, default 1) */
   int32_t ar_max_steps; uint32_t ar_when;      /* rp_set_autoreset */
+  /* rp_set_reset_table: the table [rt_rows, rt_n_o] (rt_rows = 0: none), the row cursor [1], each env's row of the latest autoreset step [N] (-1: none), the waves' ballots
+   * and first rows [(N + 255) / 256 * 4]; k_autoreset_to's grid (the waves resident at once) */
+  float* rt_tab; int rt_rows, rt_n_o; int* rt_cursor; int* rt_env_row; unsigned long long* rt_wave_bal; int* rt_wave_row; int rt_grid;
   rp_timers timers;
   char err[256];
 };
@@ -112,6 +115,7 @@ static void destroy_handle(rp_sim* h) {        /* frees whatever a (possibly par
   hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
   hipFree(h->rc_tab); hipFree(h->rc_cnt); hipFree(h->rc_ee);
   hipFree(h->ep_steps); hipFree(h->ar_list); hipFree(h->ar_ctl); hipFree(h->ar_pair);
+  hipFree(h->rt_tab); hipFree(h->rt_cursor); hipFree(h->rt_env_row); hipFree(h->rt_wave_bal); hipFree(h->rt_wave_row);
   hipFree(h->rs_state); hipFree(h->rs_idx); hipFree(h->rs_meta); hipFree(h->rs_count); hipFree(h->rs_sort_cnt); hipFree(h->rs_sort_slot); hipFree(h->rs_pair);
   if (h->rs_count_host) hipHostFree(h->rs_count_host);
   if (h->ev0) hipEventDestroy(h->ev0);
@@ -325,6 +329,16 @@ int rp_create(const rp_config* cfg, rp_handle* out) {
     h->ar_grid = min(h->ar_grid, (N + h->ar_epb - 1) / h->ar_epb);
     CREATE_CHK(hipMalloc((void**)&h->ar_pair, (size_t)4 * h->ar_grid * sizeof(int)));
     h->ar_max_steps = 0; h->ar_when = RP_AR_FAULT;
+    /* the reset table's rows and ranks; no table yet.  k_autoreset_to: one wave per env, as many as are resident at once (it strides over the list) */
+    const size_t nwv = (size_t)(N + 255) / 256 * 4;
+    CREATE_CHK(hipMalloc((void**)&h->rt_cursor, sizeof(int)));
+    CREATE_CHK(hipMemset(h->rt_cursor, 0, sizeof(int)));
+    CREATE_CHK(hipMalloc((void**)&h->rt_env_row, (size_t)N * sizeof(int)));
+    CREATE_CHK(hipMemset(h->rt_env_row, 0xff, (size_t)N * sizeof(int)));
+    CREATE_CHK(hipMalloc((void**)&h->rt_wave_bal, nwv * sizeof(unsigned long long)));
+    CREATE_CHK(hipMalloc((void**)&h->rt_wave_row, nwv * sizeof(int)));
+    CREATE_CHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_autoreset_to, 64, 0));
+    h->rt_grid = min(max(cus, 1) * max(per_cu, 1), N);
   }
   hipLaunchKernelGGL(k_init, dim3((N + 255) / 256), dim3(256), 0, 0, h->dev_model, h->state, N);
   CREATE_CHK(hipGetLastError());
@@ -434,12 +448,15 @@ int rp_reset(rp_handle h, const uint8_t* mask, const rp_out* out, void* stream) 
   return reset_impl(h, nullptr, 0, mask, out, stream);
 }
 
+/* entries of o that reset(o) reads: reset_object_pos(obs) reads object b at o[11 + 10 b : 18 + 10 b] (use_orientation) or o[7 + 6 b : 10 + 6 b] (environments.py:544-556) */
+static int reset_to_need(const DevModel* m) {
+  return m->num_objects > 0 ? (m->use_orientation ? 18 + 10 * (m->num_objects - 1) : 10 + 6 * (m->num_objects - 1))
+                            : (m->use_orientation ? (m->return_velocity ? 10 : 7) : 3);
+}
+
 int rp_reset_to(rp_handle h, const float* o, int32_t n_o, const uint8_t* mask, const rp_out* out, void* stream) {
   if (!h || !o) return RP_ERR_ARG;
-  const DevModel* m = &h->host_model;
-  /* reset_object_pos(obs) reads object b at o[11 + 10 b : 18 + 10 b] (use_orientation) or o[7 + 6 b : 10 + 6 b] (environments.py:544-556) */
-  int need = m->num_objects > 0 ? (m->use_orientation ? 18 + 10 * (m->num_objects - 1) : 10 + 6 * (m->num_objects - 1))
-                                : (m->use_orientation ? (m->return_velocity ? 10 : 7) : 3);
+  const int need = reset_to_need(&h->host_model);
   if (n_o < need) { snprintf(h->err, 256, "rp_reset_to: o has %d entries per env, this env reads %d", n_o, need); return RP_ERR_ARG; }
   return reset_impl(h, o, n_o, mask, out, stream);
 }
@@ -635,11 +652,49 @@ int rp_step_autoreset(rp_handle h, const float* action, const uint8_t* end_mask,
   const int N = h->cfg.num_envs;
   const OutPtrs op = to_ptrs(out), fp = to_ptrs(final_out);
   HIPCHK(h, hipMemsetAsync(h->ar_ctl, 0, 2 * sizeof(int), s));
+  const bool table = h->rt_rows > 0;
   hipLaunchKernelGGL(k_autoreset_mark, dim3((N + 255) / 256), dim3(256), 0, s, h->dev_model, N, (int)h->ar_max_steps, (unsigned)h->ar_when, end_mask, op, fp, done, h->ep_steps,
-                     h->ar_list, h->ar_ctl);
-  hipLaunchKernelGGL(k_autoreset, dim3(h->ar_grid), dim3(64 * SOLVE_WAVES), 0, s, h->dev_model, h->state, h->ws, (const int*)h->ar_list, h->ar_ctl, h->ar_pair, op, h->cfg.seed,
-                     (uint32_t)h->cfg.env_offset, h->ar_epb, h->debug_flags);
+                     h->ar_list, h->ar_ctl, h->rt_env_row, table ? h->rt_wave_bal : (unsigned long long*)nullptr);
+  if (table) {
+    hipLaunchKernelGGL(k_autoreset_rows, dim3(1), dim3(1024), 0, s, (const unsigned long long*)h->rt_wave_bal, (N + 63) / 64, h->rt_wave_row, h->rt_cursor, h->rt_rows);
+    hipLaunchKernelGGL(k_autoreset_to, dim3(h->rt_grid), dim3(64), 0, s, h->dev_model, h->state, (const int*)h->ar_list, (const int*)h->ar_ctl,
+                       (const unsigned long long*)h->rt_wave_bal, (const int*)h->rt_wave_row, (const float*)h->rt_tab, h->rt_rows, h->rt_n_o, h->rt_env_row, op, h->cfg.seed,
+                       (uint32_t)h->cfg.env_offset);
+  } else {
+    hipLaunchKernelGGL(k_autoreset, dim3(h->ar_grid), dim3(64 * SOLVE_WAVES), 0, s, h->dev_model, h->state, h->ws, (const int*)h->ar_list, h->ar_ctl, h->ar_pair, op, h->cfg.seed,
+                       (uint32_t)h->cfg.env_offset, h->ar_epb, h->debug_flags);
+  }
   HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+/* The table is copied into library memory on `stream`.  The device is synchronised first: steps still in flight (on any stream) may read the table this call replaces. */
+int rp_set_reset_table(rp_handle h, const float* o, int32_t rows, int32_t n_o, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  if (rows < 0) { snprintf(h->err, 256, "rp_set_reset_table: rows = %d is negative", rows); return RP_ERR_ARG; }
+  if (rows > 0) {
+    if (!o) { snprintf(h->err, 256, "rp_set_reset_table: o is NULL with rows = %d", rows); return RP_ERR_ARG; }
+    const int need = reset_to_need(&h->host_model);
+    if (n_o < need) { snprintf(h->err, 256, "rp_set_reset_table: o has %d entries per row, this env reads %d", n_o, need); return RP_ERR_ARG; }
+  }
+  DevGuard guard(h->cfg.device);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, hipDeviceSynchronize());
+  HIPCHK(h, hipFree(h->rt_tab));
+  h->rt_tab = nullptr; h->rt_rows = 0; h->rt_n_o = 0;
+  HIPCHK(h, hipMemsetAsync(h->rt_cursor, 0, sizeof(int), s));
+  if (rows == 0) return RP_OK;
+  const size_t bytes = (size_t)rows * (size_t)n_o * sizeof(float);
+  HIPCHK(h, hipMalloc((void**)&h->rt_tab, bytes));
+  HIPCHK(h, hipMemcpyAsync(h->rt_tab, o, bytes, hipMemcpyDeviceToDevice, s));
+  h->rt_rows = rows; h->rt_n_o = n_o;
+  return RP_OK;
+}
+
+int rp_get_reset_rows(rp_handle h, int32_t* dst, void* stream) {
+  if (!h || !dst) return RP_ERR_ARG;
+  DevGuard guard(h->cfg.device);
+  HIPCHK(h, hipMemcpyAsync(dst, h->rt_env_row, (size_t)h->cfg.num_envs * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return RP_OK;
 }
 

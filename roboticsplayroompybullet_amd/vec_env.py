@@ -29,13 +29,14 @@ class VecPlayEnv:
     def __init__(self, env_id, num_envs, device=0, seed=0, env_offset=0, action_type=None, goal_range_low=None, goal_range_high=None,
                  obj_lower_bound=None, obj_upper_bound=None, env_range_high=None, sparse_rew_thresh=None, sparse=True,
                  contact_margin=None, persistent_manifolds=True, hull_gjk=True, speculative_limits=False, hull_epa=None,
-                 autoreset=False, max_episode_steps=None, end_on_fault=True, end_on_success=False):
+                 autoreset=False, max_episode_steps=None, end_on_fault=True, end_on_success=False, reset_table=None):
         """The keyword arguments after env_offset up to hull_epa are the constructor kwargs of the reference's env classes that reach the
         simulation (envList.py -> environments.py:64-67); None keeps what the id registers.  contact_margin: rp_config.
 
         autoreset=True: step() ends episodes and resets the ended envs on the device (rp_step_autoreset), at the time limit
         (max_episode_steps; None = the id's _max_episode_steps, 0 = none), on a fault (end_on_fault: status & 3), on success
-        (end_on_success) and where step's end_mask is set."""
+        (end_on_success) and where step's end_mask is set.  reset_table ([M, n_o] tensor, needs autoreset): the ended envs restart from
+        its rows with reset(o) semantics instead of a settled reset(), see set_reset_table."""
         if env_id not in _lib.ENV_KINDS:
             raise NotImplementedError('env id %r is outside the hot-path scope (SURVEY.md §8)' % (env_id,))
         if not torch.cuda.is_available():
@@ -47,6 +48,11 @@ class VecPlayEnv:
         self.num_envs = int(num_envs)
         idx = device if isinstance(device, int) else (torch.device(device).index or 0)
         self.device = torch.device('cuda', idx)
+        # the simulation kwargs (random_start_table builds a handle of the same id with them)
+        self._sim_kwargs = dict(action_type=action_type, goal_range_low=goal_range_low, goal_range_high=goal_range_high, obj_lower_bound=obj_lower_bound,
+                                obj_upper_bound=obj_upper_bound, env_range_high=env_range_high, sparse_rew_thresh=sparse_rew_thresh, sparse=sparse,
+                                contact_margin=contact_margin, persistent_manifolds=persistent_manifolds, hull_gjk=hull_gjk,
+                                speculative_limits=speculative_limits, hull_epa=hull_epa)
         cfg = _lib.RpConfig(_lib.ENV_KINDS[env_id], self.num_envs, self.device.index, int(env_offset), int(seed))
         flags = 0
         if (goal_range_low is None) != (goal_range_high is None) or (obj_lower_bound is None) != (obj_upper_bound is None):
@@ -127,6 +133,12 @@ class VecPlayEnv:
             self.final['status'] = torch.zeros(N, dtype=torch.int32, device=dev)
             self.final_out = _lib.RpOut(**{k: self.final[k].data_ptr() for k in self.final})
             self._done_reason = torch.zeros(N, dtype=torch.int32, device=dev)
+            self._reset_row = torch.full((N,), -1, dtype=torch.int32, device=dev)      # info['reset_row'], owned like buf
+        self._table = None
+        if reset_table is not None:
+            if not self.autoreset:
+                raise ValueError('reset_table needs VecPlayEnv(..., autoreset=True)')
+            self.set_reset_table(reset_table)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -210,13 +222,51 @@ class VecPlayEnv:
         self._flip_pack()
         _lib.check(self.lib, self.h, self.lib.rp_step_autoreset(self.h, C.c_void_p(a.data_ptr()), mp, C.byref(self.out), C.byref(self.final_out),
                                                                 C.c_void_p(self._done_reason.data_ptr()), self._stream()), 'rp_step_autoreset')
+        if self._table is not None:
+            _lib.check(self.lib, self.h, self.lib.rp_get_reset_rows(self.h, C.c_void_p(self._reset_row.data_ptr()), self._stream()), 'rp_get_reset_rows')
         reason = self._done_reason
         info = {'is_success': self.buf['is_success'], 'target_poses': self.buf['target_poses'], 'status': self.buf['status'],
                 'terminal_observation': {k: self.final[k] for k in OBS_KEYS + ('gripper_proprioception',)},
                 'terminal_status': self.final['status'],
                 'TimeLimit.truncated': reason == _lib.DONE_TIME_LIMIT,      # gym 0.21: the time limit and nothing else ended the episode
-                'done_reason': reason}
+                'done_reason': reason,
+                'reset_row': self._reset_row}      # the table row each ended env restarted from, -1 elsewhere (and everywhere without a table)
         return self._obs(), self.buf['reward'], reason != 0, info
+
+    def set_reset_table(self, o):
+        """o [M, n_o]: the ended envs of the following autoreset steps restart from its rows with reset(o) semantics (rp_reset_to) - the ended env
+        of rank k in a step (counting ended envs in env order) takes row (cursor + k) mod M, and the cursor, 0 after this call, moves on by the step's
+        ends.  A row of obs_quat of the same id is a valid o, except on the two-object ids: reset(o) reads 28 entries there, obs_quat has 26.  None
+        removes the table: ended envs get a settled reset() again.  Synchronises the device (the table it replaces may still be read by steps in
+        flight)."""
+        if not self.autoreset:
+            raise ValueError('set_reset_table needs VecPlayEnv(..., autoreset=True)')
+        if o is None:
+            _lib.check(self.lib, self.h, self.lib.rp_set_reset_table(self.h, None, 0, 0, self._stream()), 'rp_set_reset_table')
+            self._table = None
+            self._reset_row.fill_(-1)
+            return
+        o = torch.as_tensor(o).to(device=self.device, dtype=torch.float32).contiguous()
+        assert o.dim() == 2 and o.shape[0] > 0, o.shape
+        _lib.check(self.lib, self.h, self.lib.rp_set_reset_table(self.h, C.c_void_p(o.data_ptr()), o.shape[0], o.shape[1], self._stream()),
+                   'rp_set_reset_table')
+        self._table = o      # (kept until the next set: the copy reads it when the stream gets there)
+
+    def random_start_table(self, m, seed):
+        """[m, obs_quat] float32: the obs_quat rows of m fresh reset()s (a temporary handle of this id and simulation kwargs, seed `seed`,
+        env_offset 0) - a table for set_reset_table that gives near-random starts without the settle.  reset(o) from such a row is not the
+        reset() it came from: the objects are placed at the observed poses (the play ids; the others at the observed positions, unrotated) with
+        zero velocities, where the settled ones may still have been moving; the arm is solved by IK from the rest pose toward the observed
+        end-effector position and, on the play ids, orientation - reset() aimed it at a random target with the default orientation; and the goal
+        is drawn anew (again while it is already solved).  On the play ids, reset(o) reads the blocks from o[11 + 10 b : 18 + 10 b] as the
+        reference does, which in an obs_quat row is not the block's pose; and on the two-object ids the rows are
+        shorter than what reset(o) reads (26 < 28), so set_reset_table refuses them unwidened."""
+        tmp = VecPlayEnv(self.env_id, int(m), device=self.device.index, seed=seed, **self._sim_kwargs)
+        try:
+            return tmp.reset()['obs_quat'].clone()
+        finally:
+            torch.cuda.synchronize(self.device)
+            tmp.close()
 
     @property
     def episode_steps(self):
