@@ -96,6 +96,7 @@ def load(f32=False, bullet_ref=False, abx=False):
     lib.rpo_set_margin.argtypes = [vp, C.c_double]
     lib.rpo_set_rule.argtypes = [vp, C.c_int]
     lib.rpo_last_num_tors.argtypes = [vp]
+    lib.rpo_last_collide_counts.argtypes = [vp, ip]
     lib.rpo_cache_size.argtypes = [vp, ip]
     lib.rpo_shift_free_body.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
     fp = C.POINTER(C.c_float)
@@ -427,6 +428,16 @@ class OracleEnv:
         fn = self.lib.rpo_ref_contacts if self.bullet_ref else self.lib.rpo_contacts
         n = fn(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), max_n)
         return out[:min(n, max_n)]
+
+    COLLIDE_COUNTS = ('pairs', 'candidates', 'manifolds', 'contacts', 'torsional')
+
+    def collide_counts(self):
+        """what the latest collision phase (contacts() or a substep's) wanted before each of its caps: {name: count} for COLLIDE_COUNTS - AABB-overlapping pairs
+        (cap MAX_ACTIVE_PAIRS), candidate points of the pairs examined (MAX_CANDIDATES), manifolds that wanted a slot (PM_MAX), contacts (MAX_CONTACTS), torsional
+        rows (MAX_TORS)"""
+        buf = (C.c_int * 5)()
+        self.lib.rpo_last_collide_counts(self.h, buf)
+        return dict(zip(self.COLLIDE_COUNTS, list(buf)))
 
     def arm_table(self):
         """[n_arm, 6]: jtype, lower, upper, body mass, Bullet joint index, parent dof"""

@@ -127,6 +127,8 @@ struct rpo_env {
   real finv[RP_MAX_FREE][9];        /* world inverse inertia of free bodies */
   xform xc[RP_MAX_COL]; real aabb_lo[RP_MAX_COL][3], aabb_hi[RP_MAX_COL][3];
   contact con[MAX_CONTACTS]; int ncon;
+  int wanted[5];                    /* the latest collision phase before its caps (rpo_last_collide_counts): AABB-overlapping pairs, candidate points, manifolds that wanted
+                                     * a slot, contacts, torsional rows */
   row rows[MAX_ROWS]; int nrows, n_noncontact, n_tors;
   int residual_substeps;            /* substeps so far solved in the residual form (RPO_RULE_RESIDUAL) */
   int contact_substeps;             /* substeps so far whose solve had at least one contact row (tests: where does a rollout stop being free motion) */
@@ -944,6 +946,18 @@ static int hull_box_gjk(rpo_env* e, int hc, int bc, real margin, const real* lv,
 static void pm_to_local(const rpo_env* e, int body, const real* pw, real* pl) { real t[3]; v3sub(t, pw, e->xb[body].p); m3tmulv(pl, e->xb[body].R, t); }
 static void pm_to_world(const rpo_env* e, int body, const real* pl, real* pw) { m3mulv(pw, e->xb[body].R, pl); v3add(pw, pw, e->xb[body].p); }
 static void solver_order(rpo_env* e);
+/* the torsional rows the contact list asks for before the MAX_TORS cut (build_rows' rule: one per run of contacts of one collider pair with spinning friction) */
+static void count_tors(rpo_env* e) {
+  const rp_model* m = &e->m;
+  e->wanted[4] = 0;
+  if (!(e->rule & RPO_RULE_SPIN)) return;
+  for (int ci = 0; ci < e->ncon; ci++) {
+    const contact* c = &e->con[ci];
+    if (ci > 0 && e->con[ci - 1].ca == c->ca && e->con[ci - 1].cb == c->cb) continue;
+    const real spin = (real)m->col_spin[c->ca] * (real)m->col_friction[c->cb] + (real)m->col_spin[c->cb] * (real)m->col_friction[c->ca];
+    if (spin > 0) e->wanted[4]++;
+  }
+}
 #ifdef RPO_ABX
 static int abx_gjk_epa(rpo_env* e, int a, int b, real margin, cpoint* out, int* tried, int distance_only);
 #endif
@@ -951,6 +965,7 @@ static void collide_persistent(rpo_env* e) {
   const rp_model* m = &e->m;
   contact cand[MAX_CANDIDATES]; int ncand = 0, nactive = 0;
   int act_oa[MAX_ACTIVE_PAIRS], act_ob[MAX_ACTIVE_PAIRS]; real act_thr[MAX_ACTIVE_PAIRS];
+  for (int k = 0; k < 5; k++) e->wanted[k] = 0;
   for (int pi = 0; pi < m->n_pair; pi++) {
     const int a = m->pair[pi][0], b = m->pair[pi][1];
     const real margin = e->margin >= 0 ? e->margin : (real)(m->col_thr[a] < m->col_thr[b] ? m->col_thr[a] : m->col_thr[b]);
@@ -958,6 +973,7 @@ static void collide_persistent(rpo_env* e) {
     for (int k = 0; k < 3; k++)
       if (e->aabb_lo[a][k] > e->aabb_hi[b][k] + margin || e->aabb_lo[b][k] > e->aabb_hi[a][k] + margin) sep = 1;
     if (sep) continue;
+    e->wanted[0]++;
     if (nactive >= MAX_ACTIVE_PAIRS) continue;
     act_oa[nactive] = (e->rule & RPO_RULE_XGRAN) ? 1000 + a : m->col_obj[a]; act_ob[nactive] = (e->rule & RPO_RULE_XGRAN) ? 1000 + b : m->col_obj[b]; act_thr[nactive] = (real)(m->col_thr[a] < m->col_thr[b] ? m->col_thr[a] : m->col_thr[b]); nactive++;
     cpoint pts[4]; int np = 0;
@@ -989,6 +1005,7 @@ static void collide_persistent(rpo_env* e) {
     else if (m->col_type[a] == 0 && m->col_type[b] == 0) np = box_box(e->xc[a].p, e->xc[a].R, ha, e->xc[b].p, e->xc[b].R, hb, 0, (e->rule & RPO_RULE_ODEORDER) != 0, pts);
     else if (m->col_type[a] == 0 && m->col_type[b] == 1) np = sphere_box(e->xc[b].p, hb[0], e->xc[a].p, e->xc[a].R, ha, margin, 1, pts);
     else if (m->col_type[a] == 1 && m->col_type[b] == 0) np = sphere_box(e->xc[a].p, ha[0], e->xc[b].p, e->xc[b].R, hb, margin, 0, pts);
+    e->wanted[1] += np;
     if (ncand + np > MAX_CANDIDATES) np = MAX_CANDIDATES - ncand;
     for (int i = 0; i < np; i++) {
       contact* c = &cand[ncand++];
@@ -1009,9 +1026,15 @@ static void collide_persistent(rpo_env* e) {
   }
   /* 2b. a manifold exists from the substep in which its object pair first has an AABB-overlapping collider pair (Bullet creates it in the broadphase
    * callback, before any point): creation order = row order */
+  e->wanted[2] = e->npm;
   for (int k = 0; k < nactive; k++) {
     int found = 0;
     for (int i = 0; i < e->npm; i++) if (e->pm[i].oa == act_oa[k] && e->pm[i].ob == act_ob[k]) found = 1;
+    if (!found) {                                            /* (counted once per object pair, with a slot or without) */
+      int seen = 0;
+      for (int j = 0; j < k; j++) if (act_oa[j] == act_oa[k] && act_ob[j] == act_ob[k]) seen = 1;
+      if (!seen) e->wanted[2]++;
+    }
     if (found || e->npm >= PM_MAX) continue;
     e->pm[e->npm].oa = act_oa[k]; e->pm[e->npm].ob = act_ob[k]; e->pm[e->npm].n = 0; e->pm[e->npm].thr = act_thr[k];
     e->npm++;
@@ -1116,6 +1139,7 @@ static void collide_persistent(rpo_env* e) {
         for (int i = 1; i < e->pm[mi].n; i++) if (e->pm[mi].pt[i].dist < e->pm[mi].pt[only].dist - TIE_EPS) only = i;
       }
     }
+    e->wanted[3] += only >= 0 ? 1 : e->pm[mi].n;
     for (int i = 0; i < e->pm[mi].n && e->ncon < MAX_CONTACTS; i++) {
       if (only >= 0 && i != only) continue;
       contact* c = &e->con[e->ncon++];
@@ -1162,8 +1186,9 @@ static void collide(rpo_env* e) {
 #ifdef RPO_ABX
   if ((e->rule & 2048) && collide_persist(e)) return;      /* (experiment build: the reference step's own manifold upkeep) */
 #endif
-  if ((e->rule & RPO_RULE_PERSIST) && e->margin < 0) { collide_persistent(e); return; }      /* (a uniform contact margin is a study of the stateless model: it keeps the stateless contacts, like the HIP library) */
+  if ((e->rule & RPO_RULE_PERSIST) && e->margin < 0) { collide_persistent(e); count_tors(e); return; }      /* (a uniform contact margin is a study of the stateless model: it keeps the stateless contacts, like the HIP library) */
   contact man[4]; int nman = 0, man_oa = -1, man_ob = -1, nactive = 0, ncand = 0;
+  for (int k = 0; k < 5; k++) e->wanted[k] = 0;
   for (int pi = 0; pi <= m->n_pair; pi++) {
     int a = 0, b = 0, flush = (pi == m->n_pair);
     if (!flush) {
@@ -1171,6 +1196,7 @@ static void collide(rpo_env* e) {
       if (m->col_obj[a] != man_oa || m->col_obj[b] != man_ob) flush = 1;
     }
     if (flush) {
+      e->wanted[2] += nman > 0; e->wanted[3] += nman;
       for (int i = 0; i < nman && e->ncon < MAX_CONTACTS; i++) e->con[e->ncon++] = man[i];
       nman = 0;
       if (pi == m->n_pair) break;
@@ -1181,6 +1207,7 @@ static void collide(rpo_env* e) {
     for (int k = 0; k < 3; k++)
       if (e->aabb_lo[a][k] > e->aabb_hi[b][k] + margin || e->aabb_lo[b][k] > e->aabb_hi[a][k] + margin) sep = 1;
     if (sep) continue;
+    e->wanted[0]++;
     if (nactive++ >= MAX_ACTIVE_PAIRS) continue;
     cpoint pts[4]; int np = 0;
     real ha[3], hb[3];
@@ -1206,6 +1233,7 @@ static void collide(rpo_env* e) {
       np = sphere_box(e->xc[b].p, hb[0], e->xc[a].p, e->xc[a].R, ha, margin, 1, pts);
     else if (m->col_type[a] == 1 && m->col_type[b] == 0)
       np = sphere_box(e->xc[a].p, ha[0], e->xc[b].p, e->xc[b].R, hb, margin, 0, pts);
+    e->wanted[1] += np;
     if (ncand + np > MAX_CANDIDATES) np = MAX_CANDIDATES - ncand;      /* the candidate list ends at MAX_CANDIDATES points, pairs in order */
     ncand += np;
     int kf = body_free_index(e, m->col_body[a]);
@@ -1237,6 +1265,7 @@ static void collide(rpo_env* e) {
    *   2  both halves, not arm-against-movable  block against the drawer
    *   3  both halves, arm against movable      arm against the block, the door, the button, the dial */
   solver_order(e);
+  count_tors(e);
 }
 
 /* ------------------------------------------------------------------ spatial algebra (world-origin Pluecker, [ang; lin]) */
@@ -2953,6 +2982,10 @@ int rpo_contacts(rpo_env* e, double* out, int max) {
 }
 int rpo_last_num_rows(const rpo_env* e) { return e->nrows; }
 int rpo_last_num_tors(const rpo_env* e) { return e->n_tors; }
+/* what the latest collision phase (a substep's or rpo_contacts') wanted before each of its caps, the HIP library's alike: out[0] AABB-overlapping pairs (MAX_ACTIVE_PAIRS),
+ * out[1] candidate points of the pairs examined (MAX_CANDIDATES), out[2] manifolds that wanted a slot (PM_MAX; persistent manifolds only), out[3] contacts (MAX_CONTACTS),
+ * out[4] torsional rows (MAX_TORS) */
+void rpo_last_collide_counts(const rpo_env* e, int* out) { for (int k = 0; k < 5; k++) out[k] = e->wanted[k]; }
 /* RPO_RULE_PERSIST: cached manifolds (empty ones included) and, in *points, their points */
 int rpo_cache_size(const rpo_env* e, int* points) { int n = 0; for (int i = 0; i < e->npm; i++) n += e->pm[i].n; if (points) *points = n; return e->npm; }      /* torsional rows of the latest substep (mode A) */
 int rpo_contact_substeps(const rpo_env* e) { return e->contact_substeps; }

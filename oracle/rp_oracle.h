@@ -94,6 +94,7 @@ void rpo_mass_matrix_inv(rpo_env*, double* Minv /* nv*nv, arm block via unit imp
 void rpo_forward_dynamics(rpo_env*, double* qdd /* n_arm */);
 int rpo_contacts(rpo_env*, double* out /* per contact: colA colB px py pz nx ny nz dist */, int max);
 int rpo_last_num_tors(const rpo_env* e);        /* torsional friction rows of the latest substep */
+void rpo_last_collide_counts(const rpo_env* e, int* out /* 5 */);     /* what the latest collision phase wanted before its caps: overlapping pairs, candidates, manifolds, contacts, torsional rows */
 int rpo_cache_size(const rpo_env* e, int* points);     /* RPO_RULE_PERSIST: cached manifolds (empty ones included), their points */
 /* the contact cache in the HIP library's row layout (704 words, rp_kernels.cuh PMC_*): export, and import of a row (e.g. the device's own) - tests only */
 int rpo_cache_row_words(void);

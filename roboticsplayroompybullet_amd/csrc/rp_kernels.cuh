@@ -3462,7 +3462,9 @@ __device__ __forceinline__ void copy_out(float* __restrict__ dst, const float* s
 #define AOUT_FLOATS (160 + 8 + 20)
 static_assert(W3_A % 4 == 0 && W3_ROWS % 4 == 0 && W3_ROFF % 4 == 0 && AOUT_FLOATS % 4 == 0, "16-byte copies");
 
-#define HV_MAXC 14                    /* contacts of an env on k_solve2's heavy path (heavy_solve; oracle: RES_MAX_CON) */
+#define HV_MAXC 14                    /* contacts of an env in heavy_solve's first lane register (more: heavy_solve<true>, a second register).  A register layout, no
+                                       * oracle counterpart: the oracle's residual form (solve_rows_residual) takes up to MAX_CONTACTS in one.  tests/test_contact_caps.py
+                                       * pins the caps below, and the others this file shares with the oracle, against oracle/rp_oracle.c */
 #ifndef S4_SLOTS0
 #define S4_SLOTS0 8                   /* the four-env path's contact slots: row-0 stream (arm, drawer: wave 0; oracle: RES_SLOTS0) */
 #endif
