@@ -278,6 +278,18 @@ int rp_set_reset_table(rp_handle h, const float* o, int32_t rows, int32_t n_o, v
  * while no table was set */
 int rp_get_reset_rows(rp_handle h, int32_t* dst, void* stream);
 
+/* Per-env dynamics (domain randomisation): every env has one lateral friction per collision object and one mass per free body, float32 device
+ * tables friction [N, n_obj] and mass [N, n_free]; rp_create fills them with the baked values.  A contact's friction is the product of its two
+ * objects' (at most 10), a torsional row's bound uses the other object's friction (spinning friction stays baked), a free body's mass sets its
+ * inverse mass and scales its inertia (uniform density).  The values act from the next substep that builds rows: rp_step in every pipeline, the
+ * settle substeps of rp_reset and rp_step_autoreset's resets.  They are parameters, not state: no reset changes them and rp_get_state /
+ * rp_set_state do not carry them.  Env indices are the handle's own (0 .. N-1). */
+int rp_get_dynamics_dims(rp_handle h, int32_t* n_obj, int32_t* n_free);
+/* friction [rows, n_obj] and/or mass [rows, n_free] (NULL = leave that parameter as it is), rows = 1 (broadcast) or N, into every env whose
+ * mask byte is non-zero (mask NULL = all).  Enqueued on `stream`; no host wait.  rows not 1 or N, or both arrays NULL: RP_ERR_ARG. */
+int rp_set_dynamics(rp_handle h, const float* friction, const float* mass, int32_t rows, const uint8_t* mask, void* stream);
+int rp_get_dynamics(rp_handle h, float* friction /* [N, n_obj] or NULL */, float* mass /* [N, n_free] or NULL */, void* stream);
+
 int rp_get_timers(rp_handle h, rp_timers* t);
 /* on = number of rp_step calls to keep per-launch timings for (a ring); 0 disables */
 int rp_enable_timers(rp_handle h, int32_t on);

@@ -9,6 +9,7 @@
 #include "rp_model.h"
 
 #define RP_REC_FLOATS 128 /* per-env state record, 512 B: one coalesced wave load */
+#define RP_MAX_OBJ 48     /* collision objects per env (col_obj): the per-env dynamics table's friction columns; rp_create refuses a model with more */
 
 /* state record layout (floats) */
 #ifndef RP_WIDE
@@ -104,6 +105,11 @@ typedef struct DevModel {
   int epa;                        /* ... and the expanding polytope where it finds the cores overlapping (hull_epa16; oracle RPO_RULE_EPA) */
   int persist;                    /* unless RP_CFG_STATELESS_CONTACTS: collide() keeps its manifolds in pmcache (rp_kernels.cuh PMC_*) */
   float* pmcache;                 /* [N][PMC_FLOATS], device memory owned by the handle */
+  /* per-env dynamics (rp_set_dynamics): [N][n_obj + n_free], device memory owned by the handle, filled from the bake by rp_create.  Row = the lateral friction of
+   * each collision object (col_obj), then the mass of each free body.  The kernels that build rows stage the env's row into LDS (stage_dynamics) and read it there
+   * in place of col_friction / free_mass; free_inertia scales by mass / free_mass (uniform density) where the world inverse inertia is built */
+  int n_obj;
+  float* dyn;
   /* convex-hull vertices of the arm links' collision meshes (generated/rp_hullverts_gen.h): device pointer to the arm's table (x, y, z, 0 in the owning
    * body's frame), per collider the first vertex and the count (0 = no hull).  rp_create uploads the table and sets the pointer. */
   const float* hullv;
@@ -189,6 +195,7 @@ static inline void rp_build_dev_model(const rp_model* m, DevModel* d) {
   for (int c = 0; c < m->n_col; c++) {
     d->col_body[c] = m->col_body[c]; d->col_type[c] = m->col_type[c]; d->col_link[c] = m->col_link[c]; d->col_obj[c] = m->col_obj[c];
     d->col_friction[c] = (float)m->col_friction[c];
+    if (m->col_obj[c] + 1 > d->n_obj) d->n_obj = m->col_obj[c] + 1;
     for (int k = 0; k < 3; k++) { d->col_he[c][k] = (float)m->col_he[c][k]; d->col_pos[c][k] = (float)m->col_pos[c][k]; }
     for (int k = 0; k < 9; k++) d->col_rot[c][k] = (float)m->col_rot[c][k];
   }

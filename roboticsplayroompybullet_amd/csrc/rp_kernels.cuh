@@ -111,6 +111,7 @@ struct __align__(16) EnvLds {
   float S[RP_MAX_ARM * 6];
   float Minv[144], tau[RP_MAX_ARM];
   float finv[RP_MAX_FREE * 9];
+  float dmu[RP_MAX_OBJ], dmass[RP_MAX_FREE + 1];     /* the env's row of the dynamics table (stage_dynamics) */
   float vstar[32];
   float conp[MAXC * 3], conn[MAXC * 3], cond[MAXC], conmu[MAXC];
   int cona[MAXC], conb[MAXC], conk[MAXC];     /* colliders of the contact; class: 0 no arm dof, 1 arm only, 2 spanning */
@@ -143,7 +144,7 @@ struct __align__(16) EnvLds {
  * subspaces, CRBA, Cholesky, bias forces, v*, the unit rows: 24 k) need nothing from each other, so wave 0 runs the first and wave 1 the
  * second, and only the contact rows wait for both.  What the kernel needs beyond that is resident waves: its registers (108 - 128 VGPRs) allow sixteen per CU = eight blocks, so
  * the block may take 160 KB / 8 = 20 KB of LDS and no more.  Lifetimes:
- *   whole kernel   st, body transforms, joint subspaces, the contact list, slot tables, M^-1, tau, v*, free-body inverse inertias
+ *   whole kernel   st, body transforms, joint subspaces, the contact list, slot tables, M^-1, tau, v*, free-body inverse inertias, the env's dynamics row
  *   wave 0         AABBs (dead after the broadphase: the narrowphase scratch and then the merged manifolds take their place), active-pair
  *                  tables, candidate points; the hull pool (HULL_POOL_FIELDS)
  *   wave 1         the dynamics scratch, then over it the small rows; after the join ONE CHUNK of contact rows (PREP_CH contacts: built,
@@ -171,6 +172,7 @@ struct __align__(16) PrepLds {
   alignas(16) float Minv[144];
   float tau[RP_MAX_ARM];
   float finv[RP_MAX_FREE * 9];
+  float dmu[RP_MAX_OBJ], dmass[RP_MAX_FREE + 1];
   float vstar[32];
   union alignas(16) {
     struct {                                   /* wave 1: arm_dynamics() */
@@ -447,6 +449,21 @@ __device__ __forceinline__ void joint_subspaces(const DevModel* m, LDS& L, int l
   }
 }
 
+/* the env's row of the per-env dynamics table (DevModel.dyn) into LDS: thread t < n_obj + n_free (<= 64) takes entry t.  The caller synchronises before the
+ * row is read.  env = the env's own index, never a scratch slot or a place in a group: the row belongs to the env */
+template <class LDS>
+__device__ __forceinline__ void stage_dynamics(const DevModel* m, LDS& L, int t, int env) {
+  const int no = m->n_obj, nd = no + m->n_free;
+  if (t < nd) {
+    const float v = m->dyn[(size_t)env * nd + t];
+    if (t < no) L.dmu[t] = v; else L.dmass[t - no] = v;
+  }
+}
+/* a pair's friction: the product of its two objects' (btManifoldResult::calculateCombinedFriction, clamped there at 10) */
+template <class LDS>
+__device__ __forceinline__ float pair_friction(const DevModel* m, const LDS& L, int a, int b) {
+  return fminf(L.dmu[m->col_obj[a]] * L.dmu[m->col_obj[b]], 10.f);
+}
 template <class LDS>
 __device__ __forceinline__ Xf collider_xf(const DevModel* m, const LDS& L, int c) {
   int b = m->col_body[c];
@@ -1312,7 +1329,7 @@ __device__ __forceinline__ int narrowphase_coop(const DevModel* m, LDS& L, int l
       const bool r0 = half0(ba) || half0(bdy), r1 = (ba >= 1 && !half0(ba)) || (bdy >= 1 && !half0(bdy));
       const bool arm = (ba >= 1 && ba <= n) || (bdy >= 1 && bdy <= n), movable = ba > n || bdy > n;
       L.key[ai] = m->col_obj[a] * 256 + m->col_obj[b] + (single ? 65536 : 0) + ((r0 ? (r1 ? 2 : 1) : 0) << 20) + ((arm && movable) ? (1 << 22) : 0);
-      L.pmu[ai] = m->col_friction[a] * m->col_friction[b];
+      L.pmu[ai] = pair_friction(m, L, a, b);
     }
     const int hf = act ? L.hout[ai] : -1;                    /* the hull phase's outcome for this pair: 1 hull contact (staged in L.hpt), 0 the hull says apart, -1 no hull pair / the OBB path */
     int np = 0;
@@ -1902,7 +1919,7 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
     L.conn[3 * o] = c0.w; L.conn[3 * o + 1] = c1.x; L.conn[3 * o + 2] = c1.y;
     L.cond[o] = c1.z;
     L.cona[o] = ab & 255; L.conb[o] = (ab >> 8) & 255; L.conk[o] = cls;
-    L.conmu[o] = m->persist ? m->col_friction[ab & 255] * m->col_friction[(ab >> 8) & 255] : L.pmu[(ab >> 16) & 63];      /* (a cached point's pair may not be active now: same product from the table) */
+    L.conmu[o] = m->persist ? pair_friction(m, L, ab & 255, (ab >> 8) & 255) : L.pmu[(ab >> 16) & 63];      /* (a cached point's pair may not be active now: same product from the table) */
   }
   WSYNC();
   PCLK(10)
@@ -2060,12 +2077,12 @@ __device__ __forceinline__ void unconstrained_velocities(const DevModel* m, LDS&
     }
   }
   if (lane < 32) L.vstar[lane] = lane < m->nv ? vs : 0.f;
-  if (lane < m->n_free) {     /* world inverse inertia of free body `lane` */
+  if (lane < m->n_free) {     /* world inverse inertia of free body `lane`: the baked inertia scaled by the env's mass over the baked mass (uniform density) */
     float* o = &L.finv[9 * lane];
     if (m->free_rot_locked[lane]) for (int i = 0; i < 9; i++) o[i] = 0.f;
     else {
       M3 R = ldm3(&L.xR[9 * (1 + n + lane)]);
-      V3 I = ld3(m->free_inertia[lane]);
+      V3 I = ld3(m->free_inertia[lane]) * (L.dmass[lane] / m->free_mass[lane]);
       float ii[3] = {1.f / I.x, 1.f / I.y, 1.f / I.z};
       for (int r = 0; r < 3; r++) for (int s = 0; s < 3; s++) {
         float v = 0.f;
@@ -2157,7 +2174,7 @@ __device__ __forceinline__ int tors_list(const DevModel* m, LDS& L, int lane, in
   if (lane < ncon) {
     const int a = L.cona[lane], b = L.conb[lane];
     head = lane == 0 || L.cona[lane - 1] != a || L.conb[lane - 1] != b;
-    spin = m->col_spin[a] * m->col_friction[b] + m->col_spin[b] * m->col_friction[a];
+    spin = m->col_spin[a] * L.dmu[m->col_obj[b]] + m->col_spin[b] * L.dmu[m->col_obj[a]];
   }
   const unsigned long long mk = __ballot(head && spin > 0.f);
   const int t = __popcll(mk & ((1ull << lane) - 1ull));
@@ -2244,7 +2261,7 @@ __device__ __forceinline__ void contact_rows(const DevModel* m, LDS& L, int lane
         int k = body - 1 - n, dd = dof_free(m, k);
         V3 rr = p - ld3(&L.st[ST_FREE + 13 * k]);
         V3 rxn = tors ? d : cross(rr, d);
-        float im = 1.f / m->free_mass[k];
+        float im = 1.f / L.dmass[k];
         M3 Ii = ldm3(&L.finv[9 * k]);
         V3 w = mulv(Ii, rxn);
         const V3 dl = tors ? mk3(0, 0, 0) : d;
@@ -2419,6 +2436,7 @@ __device__ float solve_rows(const DevModel* m, LDS& L, int lane, int nsmall_, in
 __device__ bool substep_heavy(const DevModel* m, EnvLds& L, int lane, int nsmall, int ncon, int nt);
 __device__ void substep(const DevModel* m, EnvLds& L, int lane, int env) {
   int n = m->n_arm;
+  stage_dynamics(m, L, lane, env);
   fk_bodies(m, L, lane);
   __syncthreads();
   joint_subspaces(m, L, lane);
@@ -3334,6 +3352,28 @@ __global__ void k_read_state(float* __restrict__ dst, const float* __restrict__ 
   dst[i] = k < RP_REC_FLOATS ? rec[env * RP_REC_FLOATS + k] : cache[env * nc + (k - RP_REC_FLOATS)];
 }
 
+/* per-env dynamics table (rp_set_dynamics / rp_get_dynamics): thread per table entry.  fr [rows][no] / ms [rows][nf] (nullptr: leave those columns), rows 1 = every
+ * env the same row; only envs whose mask byte is non-zero (mask nullptr: all) */
+static_assert(RP_MAX_OBJ + RP_MAX_FREE <= 64, "stage_dynamics: one entry of the row per thread of a wave");
+__global__ void k_set_dynamics(float* __restrict__ dyn, const float* __restrict__ fr, const float* __restrict__ ms, int rows, const uint8_t* __restrict__ mask,
+                               int N, int no, int nf) {
+  const size_t W = (size_t)(no + nf);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * W) return;
+  const size_t env = i / W, k = i % W, r = rows == 1 ? 0 : env;
+  if (mask && !mask[env]) return;
+  if (k < (size_t)no) { if (fr) dyn[i] = fr[r * no + k]; }
+  else if (ms) dyn[i] = ms[r * nf + (k - no)];
+}
+__global__ void k_get_dynamics(const float* __restrict__ dyn, float* __restrict__ fr, float* __restrict__ ms, int N, int no, int nf) {
+  const size_t W = (size_t)(no + nf);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * W) return;
+  const size_t env = i / W, k = i % W;
+  if (k < (size_t)no) { if (fr) fr[env * no + k] = dyn[i]; }
+  else if (ms) ms[env * nf + (k - no)] = dyn[i];
+}
+
 /* ------------------------------------------------------------------ split pipeline for rp_step
  * The fused substep() above needs > 256 VGPRs in its cold phases (IK, narrowphase, row build) although the hot PGS
  * loop needs ~60, so rp_step runs right-sized kernels instead:
@@ -3489,6 +3529,7 @@ __device__ __forceinline__ void prep2_core(PrepLds& L, const DevModel* __restric
   L.st[tid] = state[(size_t)env * RP_REC_FLOATS + tid];
   if (tid == 64) L.hdr[3] = pair_idx;                        /* (waits in LDS for the end of the kernel: a register held across both phases is one the narrowphase spills for) */
   if (tid == 64 && m->persist) L.hdr[2] = __float_as_int(m->pmcache[(size_t)cenv * PMC_FLOATS]);      /* the cache's manifold count, for collide() */
+  stage_dynamics(m, L, tid, cenv);
   __syncthreads();
   PCLK(16)
   if (wid == 0) fk_bodies(m, L, lane);
@@ -5303,6 +5344,7 @@ __global__ void __launch_bounds__(64) k_debug_substep(const DevModel* __restrict
   if (env >= N) return;
   load_state(L, state, env, lane);
   int n = m->n_arm;
+  stage_dynamics(m, L, lane, env);
   fk_bodies(m, L, lane);
   __syncthreads();
   joint_subspaces(m, L, lane);

@@ -28,6 +28,7 @@ struct rp_sim {
   float* hcv; int* hco;    /* their support-vertex candidate tables (DevModel.hcv / hco) */
   float* hpl;              /* their face planes, collider frame (DevModel.hpl: the ray caster) */
   float* pmcache;          /* the contact caches, [N][PMC_FLOATS] (DevModel.pmcache points here); nullptr under RP_CFG_STATELESS_CONTACTS */
+  float* dyn;              /* the per-env dynamics table, [N][n_obj + n_free] (DevModel.dyn points here) */
   int* sort_cnt;           /* [2][RP_MAX_GROUPS][SORT_BINS] load-class histograms for pairing envs in k_solve2 (double-buffered) */
   int* sort_slot;          /* [N] per env: (bin << 16) | rank inside the bin, from the latest k_solve2 */
   int* pair_env;           /* [N] per group range: env ids sorted by load class, heaviest first (k_solve2 pairs neighbours) */
@@ -112,7 +113,7 @@ const char* rp_version(void) { return "rp_playroom 0.5 (gfx950) build " RP_BUILD
 
 static void destroy_handle(rp_sim* h) {        /* frees whatever a (possibly partial) handle owns; hipFree(nullptr) etc. are no-ops */
   if (!h) return;
-  hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
+  hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dyn); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
   hipFree(h->rc_tab); hipFree(h->rc_cnt); hipFree(h->rc_ee);
   hipFree(h->ep_steps); hipFree(h->ar_list); hipFree(h->ar_ctl); hipFree(h->ar_pair);
   hipFree(h->rt_tab); hipFree(h->rt_cursor); hipFree(h->rt_env_row); hipFree(h->rt_wave_bal); hipFree(h->rt_wave_row);
@@ -291,6 +292,20 @@ int rp_create(const rp_config* cfg, rp_handle* out) {
     d->spec_limits = (cfg->flags & RP_CFG_SPECULATIVE_LIMITS) ? 1 : 0;
     if (getenv("RP_NO_SPIN") != nullptr)                     /* timing / model studies only: no torsional friction rows */
       for (int c = 0; c < RP_MAX_COL; c++) d->col_spin[c] = 0.f;
+  }
+  {      /* the per-env dynamics table, every row the bake's: each object's friction (uniform over its colliders in the bake: the first one's), each free body's mass */
+    if (d->n_obj > RP_MAX_OBJ) { snprintf(g_err, 256, "rp_create: %d collision objects, at most %d", d->n_obj, RP_MAX_OBJ); rc = RP_ERR_UNSUPPORTED; goto fail; }
+    const int nd = d->n_obj + d->n_free;
+    float row[RP_MAX_OBJ + RP_MAX_FREE];
+    for (int c = d->n_col - 1; c >= 0; c--) row[d->col_obj[c]] = d->col_friction[c];
+    for (int f = 0; f < d->n_free; f++) row[d->n_obj + f] = d->free_mass[f];
+    CREATE_CHK(hipMalloc((void**)&h->dyn, (size_t)(N + 1) * nd * sizeof(float)));      /* (+ one row behind the table: the bake's, broadcast from there) */
+    const float* base = h->dyn + (size_t)N * nd;
+    CREATE_CHK(hipMemcpy((void*)base, row, nd * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_set_dynamics, dim3((unsigned)(((size_t)N * nd + 255) / 256)), dim3(256), 0, 0, h->dyn, base, base + d->n_obj, 1, (const uint8_t*)nullptr, N,
+                       d->n_obj, d->n_free);
+    CREATE_CHK(hipGetLastError());
+    d->dyn = h->dyn;
   }
   CREATE_CHK(hipMemcpy(h->dev_model, &h->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
   CREATE_CHK(hipEventCreate(&h->ev0));
@@ -688,6 +703,36 @@ int rp_set_reset_table(rp_handle h, const float* o, int32_t rows, int32_t n_o, v
   HIPCHK(h, hipMalloc((void**)&h->rt_tab, bytes));
   HIPCHK(h, hipMemcpyAsync(h->rt_tab, o, bytes, hipMemcpyDeviceToDevice, s));
   h->rt_rows = rows; h->rt_n_o = n_o;
+  return RP_OK;
+}
+
+int rp_get_dynamics_dims(rp_handle h, int32_t* n_obj, int32_t* n_free) {
+  if (!h || !n_obj || !n_free) return RP_ERR_ARG;
+  *n_obj = h->host_model.n_obj; *n_free = h->host_model.n_free;
+  return RP_OK;
+}
+
+/* enqueued on `stream` like a step: a step queued after it on the same stream sees the new values, one queued before it the old ones */
+int rp_set_dynamics(rp_handle h, const float* friction, const float* mass, int32_t rows, const uint8_t* mask, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  const int N = h->cfg.num_envs, no = h->host_model.n_obj, nf = h->host_model.n_free;
+  if (!friction && !mass) { snprintf(h->err, 256, "rp_set_dynamics: friction and mass are both NULL"); return RP_ERR_ARG; }
+  if (rows != 1 && rows != N) { snprintf(h->err, 256, "rp_set_dynamics: rows = %d, expected 1 or num_envs = %d", rows, N); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const size_t total = (size_t)N * (no + nf);
+  hipLaunchKernelGGL(k_set_dynamics, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->dyn, friction, mass, (int)rows, mask, N, no,
+                     nf);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+int rp_get_dynamics(rp_handle h, float* friction, float* mass, void* stream) {
+  if (!h || (!friction && !mass)) { if (h) snprintf(h->err, 256, "rp_get_dynamics: friction and mass are both NULL"); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const int N = h->cfg.num_envs, no = h->host_model.n_obj, nf = h->host_model.n_free;
+  const size_t total = (size_t)N * (no + nf);
+  hipLaunchKernelGGL(k_get_dynamics, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->dyn, friction, mass, N, no, nf);
+  HIPCHK(h, hipGetLastError());
   return RP_OK;
 }
 

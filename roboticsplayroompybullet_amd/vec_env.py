@@ -5,6 +5,9 @@ is a [N, ...] torch tensor on the env's device.  State lives inside the HIP libr
 step()/reset() are owned by this object and overwritten by the next call (clone to keep).
 """
 import ctypes as C
+import json
+import math
+import os
 
 import torch
 
@@ -23,6 +26,55 @@ WIDE_STATE_LAYOUT = {'q': (0, 9), 'qd': (9, 18), 'free0': (18, 31), 'free1': (31
                      'motor_mode': (63, 72), 'motor_target': (72, 81), 'motor_maximp': (81, 90), 'goal': (90, 108),
                      'last_ee_quat': (108, 112), 'last_block_quat': (112, 116), 'last_obs_19_23': (116, 120), 'last_ag_10_14': (120, 124),
                      'have_last': (124, 125)}
+
+# registered id -> baked model (the rp_create table: arm + scene)
+MODEL_OF = {i: 'URPUUUUUPQQVVVVVVWW'[k] for i, k in _lib.ENV_KINDS.items()}
+# scene ids of the complex scene (scenes.py complex_scene, creation order) and of the push scene that the dynamics names call by name; the other
+# statics keep their bake tag (static<scene id>)
+_SCENE_NAMES = {'complex_scene': {0: 'floor', 1: 'door', 6: 'drawer', 7: 'dial', 8: 'grill', 9: 'button', 10: 'globe', 11: 'table', 12: 'cabinet_back',
+                                  13: 'cabinet_top', 14: 'cabinet_left', 15: 'cabinet_right', 16: 'block', 17: 'block2'},
+                'push_scene': {0: 'floor', 1: 'tray', 2: 'block'}, 'default_scene': {0: 'floor'}}
+
+
+def dynamics_names(model):
+    """{'friction': names of the collision objects, 'mass': names of the free bodies} of a baked model ('U', 'R', 'P', 'Q', 'V', 'W'), in the column
+    order of rp_get_dynamics: objects by their bake number (col_obj), free bodies in the record's order.  Arm links are named by their Bullet link
+    index ('link7'), the arm's fixed base 'arm_base', scene bodies as _SCENE_NAMES has them."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets', 'models.json')) as f:
+        mdl = next(m for m in json.load(f)['models'] if m['kind'] == model)
+    scene = _SCENE_NAMES[mdl['scene']]
+    jointed = {j['scene_id'] for j in mdl['joint1']}
+
+    def name(tag, link):
+        if tag == 'arm':
+            return 'link%d' % link
+        if tag.startswith('joint1_'):
+            return scene.get(int(tag[7:]), tag)
+        if tag.startswith('static') or tag.startswith('free'):
+            sid = int(tag.lstrip('staticfre'))
+            return scene[sid] + '_base' if sid in jointed and sid in scene else scene.get(sid, tag)      # (the static base of a scene joint's body)
+        return tag
+
+    objs = {}
+    for c in mdl['col']:
+        objs.setdefault(c['obj'], name(c['tag'], c['link']))
+    fr = [objs[o] for o in range(len(objs))]
+    ms = [scene[b['scene_id']] for b in mdl['free']]
+    assert len(set(fr)) == len(fr) and len(set(ms)) == len(ms), (fr, ms)
+    return {'friction': tuple(fr), 'mass': tuple(ms)}
+
+
+def check_dynamics_values(what, v):
+    """a host-side friction / mass value (number, sequence, numpy array, CPU tensor) as a float32 CPU tensor; friction must be >= 0, mass > 0, both
+    finite (ValueError otherwise)"""
+    t = torch.as_tensor(v, dtype=torch.float32, device='cpu')
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError('%s: values must be finite' % what)
+    if what == 'mass' and not bool((t > 0).all()):
+        raise ValueError('mass: values must be > 0')
+    if what == 'friction' and not bool((t >= 0).all()):
+        raise ValueError('friction: values must be >= 0')
+    return t
 
 
 class VecPlayEnv:
@@ -282,6 +334,64 @@ class VecPlayEnv:
         assert t.shape == (self.num_envs,), t.shape
         _lib.check(self.lib, self.h, self.lib.rp_set_episode_steps(self.h, C.c_void_p(t.data_ptr()), self._stream()), 'rp_set_episode_steps')
         self._ep_src = t      # (kept until the next set: the copy reads it when the stream gets there)
+
+    @property
+    def dynamics_names(self):
+        """{'friction': a name per collision object, 'mass': a name per free body}: the columns of get_dynamics / set_dynamics"""
+        return dynamics_names(MODEL_OF[self.env_id])
+
+    def get_dynamics(self):
+        """{'friction': [N, n_obj], 'mass': [N, n_free]} float32 device tensors: every env's lateral friction per collision object and mass per
+        free body (a fresh handle: the baked values)"""
+        no, nf = C.c_int32(), C.c_int32()
+        _lib.check(self.lib, self.h, self.lib.rp_get_dynamics_dims(self.h, C.byref(no), C.byref(nf)), 'rp_get_dynamics_dims')
+        fr = torch.empty((self.num_envs, no.value), dtype=torch.float32, device=self.device)
+        ms = torch.empty((self.num_envs, nf.value), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib, self.h, self.lib.rp_get_dynamics(self.h, C.c_void_p(fr.data_ptr()), C.c_void_p(ms.data_ptr()) if nf.value else None,
+                                                              self._stream()), 'rp_get_dynamics')
+        return {'friction': fr, 'mass': ms}
+
+    def set_dynamics(self, friction=None, mass=None, mask=None):
+        """Per-env lateral friction per collision object ([N, n_obj] or [n_obj]: every env the same) and / or mass per free body ([N, n_free] or
+        [n_free]) for the envs where mask [N] != 0 (None: all); None leaves that parameter as it is.  A contact's friction is the product of its
+        objects' (at most 10); a body's inertia scales with its mass.  The values act from the next step or reset substep on this stream, and no
+        reset changes them.  Host values (numbers, numpy, CPU tensors) are checked (friction >= 0, mass > 0, finite); tensors on the env's device
+        are passed through without a host read, so the call can sit in a device-side loop (e.g. mask=done)."""
+        if friction is None and mass is None:
+            raise ValueError('set_dynamics: give friction, mass or both')
+        no, nf = C.c_int32(), C.c_int32()
+        _lib.check(self.lib, self.h, self.lib.rp_get_dynamics_dims(self.h, C.byref(no), C.byref(nf)), 'rp_get_dynamics_dims')
+        N = self.num_envs
+
+        def prep(what, v, k):
+            if v is None:
+                return None, 0
+            on_dev = isinstance(v, torch.Tensor) and v.device == self.device
+            t = v.to(dtype=torch.float32) if on_dev else check_dynamics_values(what, v).to(self.device)
+            if t.dim() == 0 and not on_dev:
+                t = t.expand(k)
+            if t.dim() == 1 and t.shape[0] == k:
+                return t.contiguous(), 1
+            if t.dim() == 2 and t.shape == (N, k):
+                return t.contiguous(), N
+            raise ValueError('set_dynamics: %s has shape %s, expected [%d] or [%d, %d]' % (what, tuple(t.shape), k, N, k))
+
+        fr, rf = prep('friction', friction, no.value)
+        ms, rm = prep('mass', mass, nf.value)
+        if fr is not None and ms is not None and rf != rm:      # one call, one row count: broadcast the single row
+            fr, ms = (fr.expand(N, -1).contiguous(), ms) if rf == 1 else (fr, ms.expand(N, -1).contiguous())
+        rows = rf or rm
+        mp = None
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous() if isinstance(mask, torch.Tensor) else \
+                torch.as_tensor(mask, dtype=torch.uint8).to(self.device)
+            if mask.shape != (N,):
+                raise ValueError('set_dynamics: mask has shape %s, expected [%d]' % (tuple(mask.shape), N))
+            mp = C.c_void_p(mask.data_ptr())
+        _lib.check(self.lib, self.h, self.lib.rp_set_dynamics(self.h, C.c_void_p(fr.data_ptr()) if fr is not None else None,
+                                                              C.c_void_p(ms.data_ptr()) if ms is not None and ms.numel() else None, rows, mp,
+                                                              self._stream()), 'rp_set_dynamics')
+        self._dyn_src = (fr, ms, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
 
     def calc_state(self):
         self._flip_pack()
