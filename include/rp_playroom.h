@@ -290,6 +290,20 @@ int rp_get_dynamics_dims(rp_handle h, int32_t* n_obj, int32_t* n_free);
 int rp_set_dynamics(rp_handle h, const float* friction, const float* mass, int32_t rows, const uint8_t* mask, void* stream);
 int rp_get_dynamics(rp_handle h, float* friction /* [N, n_obj] or NULL */, float* mass /* [N, n_free] or NULL */, void* stream);
 
+/* Per-env external wrenches (pushes, disturbances, payloads, gravity compensation): every env has, for each of its moving bodies, a force through the body's centre
+ * of mass and a torque, both in world coordinates, float32 device table wrench [N, n_body, 6] = fx fy fz tx ty tz.  Bodies in column order: the arm's n_arm links
+ * (one per dof, in dof order), the n_free free bodies in the record's order, the n_j1 scene-joint bodies; n_body is their sum.  A free body gains dt f / mass (the env's
+ * mass, rp_set_dynamics) and dt R I^-1 R^T t (a rotation-locked body ignores the torque); an arm link's wrench enters the joint torques as -J_com^T f - J_w^T t; a
+ * scene joint takes axis . f (prismatic) or axis . t (revolute; the force acts at the joint frame's origin).  The wrench is held: it acts in every substep, from the
+ * next substep that builds rows (rp_step in every pipeline, the settle substeps of rp_reset, rp_step_autoreset's resets) until the caller changes it.  It is a
+ * parameter, not state: rp_create zeroes it, no reset changes it and rp_get_state / rp_set_state do not carry it.  A zero entry leaves every result bit for bit what it
+ * is without a table.  Env indices are the handle's own (0 .. N-1). */
+int rp_get_wrench_dims(rp_handle h, int32_t* n_arm, int32_t* n_free, int32_t* n_j1);
+/* wrench [rows, n_body, 6], rows = 1 (broadcast) or N, into every env whose mask byte is non-zero (mask NULL = all).  Enqueued on `stream`; no host wait.
+ * wrench NULL: zero the masked envs' rows.  rows not 1 or N: RP_ERR_ARG. */
+int rp_set_wrench(rp_handle h, const float* wrench, int32_t rows, const uint8_t* mask, void* stream);
+int rp_get_wrench(rp_handle h, float* wrench /* [N, n_body, 6] */, void* stream);
+
 int rp_get_timers(rp_handle h, rp_timers* t);
 /* on = number of rp_step calls to keep per-launch timings for (a ring); 0 disables */
 int rp_enable_timers(rp_handle h, int32_t on);

@@ -110,6 +110,10 @@ typedef struct DevModel {
    * in place of col_friction / free_mass; free_inertia scales by mass / free_mass (uniform density) where the world inverse inertia is built */
   int n_obj;
   float* dyn;
+  /* per-env wrenches (rp_set_wrench): [N][nbody - 1][6], device memory owned by the handle, zeroed by rp_create.  Row = per moving body (arm links in dof order, free
+   * bodies, scene-joint bodies) a world force through its centre of mass and a world torque; arm_dynamics / unconstrained_velocities read the entries of the bodies
+   * whose dofs their lanes own (ld_wrench) */
+  const float* wrench;
   /* convex-hull vertices of the arm links' collision meshes (generated/rp_hullverts_gen.h): device pointer to the arm's table (x, y, z, 0 in the owning
    * body's frame), per collider the first vertex and the count (0 = no hull).  rp_create uploads the table and sets the pointer. */
   const float* hullv;

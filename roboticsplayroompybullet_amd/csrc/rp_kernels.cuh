@@ -464,6 +464,14 @@ template <class LDS>
 __device__ __forceinline__ float pair_friction(const DevModel* m, const LDS& L, int a, int b) {
   return fminf(L.dmu[m->col_obj[a]] * L.dmu[m->col_obj[b]], 10.f);
 }
+/* the per-env wrench table (DevModel.wrench, rp_set_wrench): half a row entry of moving body `body` (arm links 0 .. n_arm-1 in dof order, then the free bodies, then
+ * the scene-joint bodies) of env `env` - the world force through the centre of mass (half 0) or the world torque (half 1).  Read straight from global memory by the lane
+ * that owns the body's dof; env = the env's own index, as in stage_dynamics.  Every term a wrench adds stands behind wrench_on(): a zero entry runs the code that ran
+ * before there was a table, so no bit moves (x + 0.0f is not x for x = -0.0f) */
+__device__ __forceinline__ V3 ld_wrench(const DevModel* m, int env, int body, int half) {
+  return ld3(m->wrench + ((size_t)env * (m->nbody - 1) + body) * 6 + 3 * half);
+}
+__device__ __forceinline__ bool wrench_on(V3 w) { return w.x != 0.f || w.y != 0.f || w.z != 0.f; }
 template <class LDS>
 __device__ __forceinline__ Xf collider_xf(const DevModel* m, const LDS& L, int c) {
   int b = m->col_body[c];
@@ -1928,9 +1936,11 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
 
 /* ------------------------------------------------------------------ arm dynamics: CRBA mass matrix, RNEA bias, inverse */
 template <class LDS>
-__device__ __forceinline__ void arm_dynamics(const DevModel* m, LDS& L, int lane) {
+__device__ __forceinline__ void arm_dynamics(const DevModel* m, LDS& L, int lane, int env) {
   int n = m->n_arm;
   V3 O = ld3(L.O);
+  V3 wf = mk3(0, 0, 0), wt = mk3(0, 0, 0);      /* the env's wrench on link `lane` (asked for here, needed where the bias forces are built) */
+  if (lane < n) { wf = ld_wrench(m, env, lane, 0); wt = ld_wrench(m, env, lane, 1); }
   if (lane < n) {      /* own spatial inertia about O: (m, h = m c, Ibar = R Ic R^T - m [c]x^2) */
     M3 R = ldm3(&L.xR[9 * (1 + lane)]);
     V3 c = ld3(&L.xp[3 * (1 + lane)]) + mulv(R, ld3(m->arm_com[lane])) - O;
@@ -1983,7 +1993,12 @@ __device__ __forceinline__ void arm_dynamics(const DevModel* m, LDS& L, int lane
     for (int j = 0; j < n; j++) { V6 cj = ld6(&L.csp[6 * j]); bool on = (anc >> j) & 1u; a.a = a.a + (on ? cj.a : mk3(0, 0, 0)); a.l = a.l + (on ? cj.l : mk3(0, 0, 0)); }
     V6 v = ld6(&L.vsp[6 * lane]);
     const float* I = &L.inert[10 * lane];
-    st6(&L.fsp[6 * lane], inertia_mul(I, a) + crf(v, inertia_mul(I, v)));
+    V6 fb = inertia_mul(I, a) + crf(v, inertia_mul(I, v));
+    if (wrench_on(wf) || wrench_on(wt)) {      /* external wrench: minus its spatial force about O (force at the link's centre of mass), so that tau = tau0 - J_com^T f - J_w^T t */
+      V3 c = ld3(&L.xp[3 * (1 + lane)]) + mulv(ldm3(&L.xR[9 * (1 + lane)]), ld3(m->arm_com[lane])) - O;
+      fb.a = fb.a - (wt + cross(c, wf)); fb.l = fb.l - wf;
+    }
+    st6(&L.fsp[6 * lane], fb);
   }
   WSYNC();
   if (lane < n) {
@@ -2039,9 +2054,12 @@ __device__ __forceinline__ void arm_dynamics(const DevModel* m, LDS& L, int lane
 
 /* unconstrained velocities v* = v + dt * a for every dof (lane = dof) */
 template <class LDS>
-__device__ __forceinline__ void unconstrained_velocities(const DevModel* m, LDS& L, int lane) {
+__device__ __forceinline__ void unconstrained_velocities(const DevModel* m, LDS& L, int lane, int env) {
   int n = m->n_arm;
   float vs = 0.f;
+  V3 wv = mk3(0, 0, 0);      /* what this lane's dof feels of the env's wrench: a free body's force (linear dofs) or torque (angular), a scene joint's force (prismatic) or torque */
+  if (lane >= n && lane < n + 6 * m->n_free) wv = ld_wrench(m, env, n + (lane - n) / 6, (lane - n) % 6 >= 3);
+  else if (lane >= n && lane < m->nv) wv = ld_wrench(m, env, lane - 5 * m->n_free, m->j1_type[lane - n - 6 * m->n_free] != 1);
   if (lane < n) {
     float qdd = 0.f;
     for (int k = 0; k < n; k++) qdd -= L.Minv[lane * 12 + k] * L.tau[k];
@@ -2053,6 +2071,7 @@ __device__ __forceinline__ void unconstrained_velocities(const DevModel* m, LDS&
       V3 v = ld3(f + 7);
       float vn = norm(v);
       vs = comp(v, c) + K_DT * (-(K_LIN_DAMP + K_LIN_DAMP * vn) * comp(v, c)) + (c == 2 ? K_DT * K_GRAVITY : 0.f);
+      if (comp(wv, c) != 0.f) vs += K_DT * comp(wv, c) / L.dmass[k];
     } else if (!m->free_rot_locked[k]) {
       M3 R = ldm3(&L.xR[9 * (1 + n + k)]);
       V3 w = ld3(f + 10);
@@ -2064,6 +2083,10 @@ __device__ __forceinline__ void unconstrained_velocities(const DevModel* m, LDS&
       V3 al = mk3((-g.x - Iw.x * kd) / I.x, (-g.y - Iw.y * kd) / I.y, (-g.z - Iw.z * kd) / I.z);
       V3 aw = mulv(R, al);
       vs = comp(w, c - 3) + K_DT * comp(aw, c - 3);
+      if (wrench_on(wv)) {      /* R I^-1 R^T torque, the inertia scaled by the env's mass as finv's below */
+        V3 tl = tmulv(R, wv), Is = I * (L.dmass[k] / m->free_mass[k]);
+        vs += K_DT * comp(mulv(R, mk3(tl.x / Is.x, tl.y / Is.y, tl.z / Is.z)), c - 3);
+      }
     }
   } else if (lane < m->nv) {
     int k = lane - n - 6 * m->n_free;
@@ -2075,6 +2098,8 @@ __device__ __forceinline__ void unconstrained_velocities(const DevModel* m, LDS&
     } else {
       vs = qd + K_DT * (-(K_ANG_DAMP + K_ANG_DAMP * fabsf(qd)) * qd);
     }
+    if (wrench_on(wv))      /* generalised force: the world axis times the force (prismatic) or the torque (revolute) */
+      vs += K_DT * (dot(mulv(ldm3(&L.xR[9 * (1 + n + m->n_free + k)]), ld3(m->j1_axis[k])), wv) * m->j1_minv[k]);
   }
   if (lane < 32) L.vstar[lane] = lane < m->nv ? vs : 0.f;
   if (lane < m->n_free) {     /* world inverse inertia of free body `lane`: the baked inertia scaled by the env's mass over the baked mass (uniform density) */
@@ -2443,8 +2468,8 @@ __device__ void substep(const DevModel* m, EnvLds& L, int lane, int env) {
   collider_aabbs(m, L, lane);
   __syncthreads();
   int ncon = collide(m, L, lane, env);
-  arm_dynamics(m, L, lane);
-  unconstrained_velocities(m, L, lane);
+  arm_dynamics(m, L, lane, env);
+  unconstrained_velocities(m, L, lane, env);
   int nsmall = build_small_rows(m, L, lane);
   const int nt = tors_list(m, L, lane, ncon);
   WSYNC();
@@ -3374,6 +3399,20 @@ __global__ void k_get_dynamics(const float* __restrict__ dyn, float* __restrict_
   else if (ms) ms[env * nf + (k - no)] = dyn[i];
 }
 
+/* per-env wrench table (rp_set_wrench / rp_get_wrench): thread per table entry.  src [rows][W] (nullptr: zeros), rows 1 = every env the same row; only envs whose
+ * mask byte is non-zero (mask nullptr: all) */
+__global__ void k_set_wrench(float* __restrict__ tab, const float* __restrict__ src, int rows, const uint8_t* __restrict__ mask, int N, int W) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * W) return;
+  const size_t env = i / W, k = i % W;
+  if (mask && !mask[env]) return;
+  tab[i] = src ? src[(rows == 1 ? 0 : env) * W + k] : 0.f;
+}
+__global__ void k_get_wrench(const float* __restrict__ tab, float* __restrict__ dst, size_t total) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < total) dst[i] = tab[i];
+}
+
 /* ------------------------------------------------------------------ split pipeline for rp_step
  * The fused substep() above needs > 256 VGPRs in its cold phases (IK, narrowphase, row build) although the hot PGS
  * loop needs ~60, so rp_step runs right-sized kernels instead:
@@ -3552,8 +3591,8 @@ __device__ __forceinline__ void prep2_core(PrepLds& L, const DevModel* __restric
     /* ---- wave 1: the arm's dynamics, v*, the unit rows (motors, limits, gear, scene-joint motors) in the solver's dof-indexed form */
     joint_subspaces(m, L, lane);
     PCLK(18)
-    arm_dynamics(m, L, lane);
-    unconstrained_velocities(m, L, lane);
+    arm_dynamics(m, L, lane, cenv);
+    unconstrained_velocities(m, L, lane, cenv);
     PCLK(3)
     int nsmall = build_small_rows(m, L, lane);
     nsmall = uni(nsmall);
@@ -5360,8 +5399,8 @@ __global__ void __launch_bounds__(64) k_debug_substep(const DevModel* __restrict
       o[8] = L.cond[c];
     }
   }
-  arm_dynamics(m, L, lane);
-  unconstrained_velocities(m, L, lane);
+  arm_dynamics(m, L, lane, env);
+  unconstrained_velocities(m, L, lane, env);
   if (env == dbg_env && lane == 0) {
     for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) dbg[320 + i * 12 + j] = L.Minv[i * 12 + j];
     for (int i = 0; i < 32; i++) dbg[480 + i] = L.vstar[i];

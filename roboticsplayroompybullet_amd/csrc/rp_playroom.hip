@@ -29,6 +29,7 @@ struct rp_sim {
   float* hpl;              /* their face planes, collider frame (DevModel.hpl: the ray caster) */
   float* pmcache;          /* the contact caches, [N][PMC_FLOATS] (DevModel.pmcache points here); nullptr under RP_CFG_STATELESS_CONTACTS */
   float* dyn;              /* the per-env dynamics table, [N][n_obj + n_free] (DevModel.dyn points here) */
+  float* wrench;           /* the per-env wrench table, [N][n_arm + n_free + n_j1][6] (DevModel.wrench points here) */
   int* sort_cnt;           /* [2][RP_MAX_GROUPS][SORT_BINS] load-class histograms for pairing envs in k_solve2 (double-buffered) */
   int* sort_slot;          /* [N] per env: (bin << 16) | rank inside the bin, from the latest k_solve2 */
   int* pair_env;           /* [N] per group range: env ids sorted by load class, heaviest first (k_solve2 pairs neighbours) */
@@ -106,14 +107,14 @@ extern "C" {
 #define RP_BUILD_ID "unversioned"
 #endif
 #ifdef RP_WIDE
-const char* rp_version(void) { return "rp_playroom 0.5 (gfx950, wide build: two-object play ids) build " RP_BUILD_ID; }
+const char* rp_version(void) { return "rp_playroom 0.5.1 (gfx950, wide build: two-object play ids) build " RP_BUILD_ID; }
 #else
-const char* rp_version(void) { return "rp_playroom 0.5 (gfx950) build " RP_BUILD_ID; }
+const char* rp_version(void) { return "rp_playroom 0.5.1 (gfx950) build " RP_BUILD_ID; }
 #endif
 
 static void destroy_handle(rp_sim* h) {        /* frees whatever a (possibly partial) handle owns; hipFree(nullptr) etc. are no-ops */
   if (!h) return;
-  hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dyn); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
+  hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dyn); hipFree(h->wrench); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
   hipFree(h->rc_tab); hipFree(h->rc_cnt); hipFree(h->rc_ee);
   hipFree(h->ep_steps); hipFree(h->ar_list); hipFree(h->ar_ctl); hipFree(h->ar_pair);
   hipFree(h->rt_tab); hipFree(h->rt_cursor); hipFree(h->rt_env_row); hipFree(h->rt_wave_bal); hipFree(h->rt_wave_row);
@@ -306,6 +307,12 @@ int rp_create(const rp_config* cfg, rp_handle* out) {
                        d->n_obj, d->n_free);
     CREATE_CHK(hipGetLastError());
     d->dyn = h->dyn;
+  }
+  {      /* the per-env wrench table: nothing pushes until rp_set_wrench says so */
+    const size_t bytes = (size_t)N * (d->nbody - 1) * 6 * sizeof(float);
+    CREATE_CHK(hipMalloc((void**)&h->wrench, bytes));
+    CREATE_CHK(hipMemset(h->wrench, 0, bytes));
+    d->wrench = h->wrench;
   }
   CREATE_CHK(hipMemcpy(h->dev_model, &h->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
   CREATE_CHK(hipEventCreate(&h->ev0));
@@ -732,6 +739,33 @@ int rp_get_dynamics(rp_handle h, float* friction, float* mass, void* stream) {
   const int N = h->cfg.num_envs, no = h->host_model.n_obj, nf = h->host_model.n_free;
   const size_t total = (size_t)N * (no + nf);
   hipLaunchKernelGGL(k_get_dynamics, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->dyn, friction, mass, N, no, nf);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+int rp_get_wrench_dims(rp_handle h, int32_t* n_arm, int32_t* n_free, int32_t* n_j1) {
+  if (!h || !n_arm || !n_free || !n_j1) return RP_ERR_ARG;
+  *n_arm = h->host_model.n_arm; *n_free = h->host_model.n_free; *n_j1 = h->host_model.n_j1;
+  return RP_OK;
+}
+
+/* enqueued on `stream` like rp_set_dynamics: a step queued after it on the same stream feels the new wrenches from its first substep, one queued before it the old ones */
+int rp_set_wrench(rp_handle h, const float* wrench, int32_t rows, const uint8_t* mask, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  const int N = h->cfg.num_envs, W = 6 * (h->host_model.nbody - 1);
+  if (rows != 1 && rows != N) { snprintf(h->err, 256, "rp_set_wrench: rows = %d, expected 1 or num_envs = %d", rows, N); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const size_t total = (size_t)N * W;
+  hipLaunchKernelGGL(k_set_wrench, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->wrench, wrench, (int)rows, mask, N, W);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+int rp_get_wrench(rp_handle h, float* wrench, void* stream) {
+  if (!h || !wrench) { if (h) snprintf(h->err, 256, "rp_get_wrench: wrench is NULL"); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const size_t total = (size_t)h->cfg.num_envs * 6 * (h->host_model.nbody - 1);
+  hipLaunchKernelGGL(k_get_wrench, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->wrench, wrench, total);
   HIPCHK(h, hipGetLastError());
   return RP_OK;
 }

@@ -77,6 +77,27 @@ def check_dynamics_values(what, v):
     return t
 
 
+def wrench_names(model):
+    """names of the moving bodies of a baked model, in the column order of rp_get_wrench: the arm's links by their Bullet link index ('link7', one per
+    dof, in dof order), the free bodies as dynamics_names' 'mass' calls them ('block', 'drawer', ...), the scene-joint bodies by their scene name
+    ('door', 'button', 'dial')"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets', 'models.json')) as f:
+        mdl = next(m for m in json.load(f)['models'] if m['kind'] == model)
+    scene = _SCENE_NAMES[mdl['scene']]
+    names = ['link%d' % a['bullet_index'] for a in mdl['arm']] + list(dynamics_names(model)['mass']) + \
+        [scene.get(j['scene_id'], 'joint1_%d' % j['scene_id']) for j in mdl['joint1']]
+    assert len(set(names)) == len(names), names
+    return tuple(names)
+
+
+def check_wrench_values(v):
+    """a host-side wrench (sequence, numpy array, CPU tensor) as a float32 CPU tensor; every value finite (ValueError otherwise)"""
+    t = torch.as_tensor(v, dtype=torch.float32, device='cpu')
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError('wrench: values must be finite')
+    return t
+
+
 class VecPlayEnv:
     def __init__(self, env_id, num_envs, device=0, seed=0, env_offset=0, action_type=None, goal_range_low=None, goal_range_high=None,
                  obj_lower_bound=None, obj_upper_bound=None, env_range_high=None, sparse_rew_thresh=None, sparse=True,
@@ -392,6 +413,71 @@ class VecPlayEnv:
                                                               C.c_void_p(ms.data_ptr()) if ms is not None and ms.numel() else None, rows, mp,
                                                               self._stream()), 'rp_set_dynamics')
         self._dyn_src = (fr, ms, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
+
+    @property
+    def wrench_names(self):
+        """a name per moving body: the body columns of get_wrench / set_wrench (arm links, free bodies, scene-joint bodies)"""
+        return wrench_names(MODEL_OF[self.env_id])
+
+    def _n_body(self):
+        na, nf, nj = C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(self.lib, self.h, self.lib.rp_get_wrench_dims(self.h, C.byref(na), C.byref(nf), C.byref(nj)), 'rp_get_wrench_dims')
+        return na.value + nf.value + nj.value
+
+    def _mask(self, what, mask):
+        if mask is None:
+            return None
+        mask = mask.to(device=self.device, dtype=torch.uint8).contiguous() if isinstance(mask, torch.Tensor) else \
+            torch.as_tensor(mask, dtype=torch.uint8).to(self.device)
+        if mask.shape != (self.num_envs,):
+            raise ValueError('%s: mask has shape %s, expected [%d]' % (what, tuple(mask.shape), self.num_envs))
+        return mask
+
+    def get_wrench(self):
+        """[N, n_body, 6] float32 device tensor: every env's external force (through the centre of mass) and torque on each moving body, world
+        coordinates, fx fy fz tx ty tz (a fresh handle: zeros)"""
+        w = torch.empty((self.num_envs, self._n_body(), 6), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib, self.h, self.lib.rp_get_wrench(self.h, C.c_void_p(w.data_ptr()), self._stream()), 'rp_get_wrench')
+        return w
+
+    def set_wrench(self, wrench, mask=None):
+        """External wrenches ([N, n_body, 6], or [n_body, 6]: every env the same; None: zero) for the envs where mask [N] != 0 (None: all).  Bodies as
+        wrench_names has them; per body a world force through its centre of mass and a world torque.  They act in every substep from the next step or
+        reset substep on this stream until they are set again; no reset changes them.  Host values (sequences, numpy, CPU tensors) are checked finite;
+        tensors on the env's device are passed through without a host read, so the call can sit in a device-side loop (set_wrench(None, mask=done))."""
+        N, nb = self.num_envs, self._n_body()
+        w, rows = None, 1
+        if wrench is not None:
+            on_dev = isinstance(wrench, torch.Tensor) and wrench.device == self.device
+            w = wrench.to(dtype=torch.float32) if on_dev else check_wrench_values(wrench).to(self.device)
+            if tuple(w.shape) == (nb, 6):
+                rows = 1
+            elif tuple(w.shape) == (N, nb, 6):
+                rows = N
+            else:
+                raise ValueError('set_wrench: wrench has shape %s, expected [%d, 6] or [%d, %d, 6]' % (tuple(w.shape), nb, N, nb))
+            w = w.contiguous()
+        mask = self._mask('set_wrench', mask)
+        _lib.check(self.lib, self.h, self.lib.rp_set_wrench(self.h, C.c_void_p(w.data_ptr()) if w is not None else None, rows,
+                                                            C.c_void_p(mask.data_ptr()) if mask is not None else None, self._stream()), 'rp_set_wrench')
+        self._wrench_src = (w, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
+
+    def push(self, body, force=None, torque=None, mask=None):
+        """Set the force and / or the torque (3 values, or [N, 3]; None leaves that half as it is) on one body of wrench_names for the envs where
+        mask != 0 (None: all), the other bodies' wrenches untouched: a read-modify-write of the table on the device."""
+        if force is None and torque is None:
+            raise ValueError('push: give force, torque or both')
+        b = self.wrench_names.index(body)
+        w = self.get_wrench()
+        for half, v in ((0, force), (1, torque)):
+            if v is None:
+                continue
+            on_dev = isinstance(v, torch.Tensor) and v.device == self.device
+            t = v.to(dtype=torch.float32) if on_dev else check_wrench_values(v).to(self.device)
+            if tuple(t.shape) not in ((3,), (self.num_envs, 3)):
+                raise ValueError('push: %s has shape %s, expected [3] or [%d, 3]' % (('force', 'torque')[half], tuple(t.shape), self.num_envs))
+            w[:, b, 3 * half:3 * half + 3] = t
+        self.set_wrench(w, mask=mask)
 
     def calc_state(self):
         self._flip_pack()

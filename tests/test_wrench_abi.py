@@ -1,0 +1,102 @@
+"""Per-env external wrenches (rp_get_wrench_dims / rp_set_wrench / rp_get_wrench) on a GPU-less host: declared in include/rp_playroom.h, exported by both
+libraries together with their kernels, mirrored in _lib and VecPlayEnv; the body names against the bake and against dynamics_names; the host-side value
+checks."""
+import ctypes
+import inspect
+import json
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ('rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench')
+KINDS = ('U', 'R', 'P', 'Q', 'V', 'W')
+
+
+def _header():
+    src = open(os.path.join(REPO, 'include', 'rp_playroom.h')).read()
+    return re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+
+
+def _decl(src, name):
+    return ' '.join(re.search(r'int %s\((.*?)\);' % name, src, flags=re.S).group(1).replace(',', ' , ').split())
+
+
+def test_entry_points_are_declared():
+    src = _header()
+    assert _decl(src, 'rp_get_wrench_dims') == 'rp_handle h , int32_t* n_arm , int32_t* n_free , int32_t* n_j1'
+    assert _decl(src, 'rp_set_wrench') == 'rp_handle h , const float* wrench , int32_t rows , const uint8_t* mask , void* stream'
+    assert _decl(src, 'rp_get_wrench') == 'rp_handle h , float* wrench , void* stream'
+
+
+def test_entry_points_are_exported_by_both_libraries_and_mirrored():
+    from roboticsplayroompybullet_amd import _lib
+    _lib.build()
+    for path in (_lib.LIB_PATH, _lib.WIDE_LIB_PATH):
+        out = subprocess.run(['nm', '-D', '--defined-only', path], check=True, capture_output=True, text=True).stdout
+        exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == 'T'}
+        for name in NEW:
+            assert name in exported, (name, path)
+        blob = open(path, 'rb').read()
+        assert b'k_set_wrench' in blob and b'k_get_wrench' in blob, path
+    for name in NEW:
+        assert name in _lib.EXPORTS, name
+    vp, ip = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)
+    for wide in (False, True):
+        lib = _lib.load(wide=wide)
+        assert lib.rp_get_wrench_dims.argtypes == [vp, ip, ip, ip]
+        assert lib.rp_set_wrench.argtypes == [vp, vp, ctypes.c_int32, vp, vp]
+        assert lib.rp_get_wrench.argtypes == [vp, vp, vp]
+
+
+def test_vec_env_has_the_wrench_methods():
+    from roboticsplayroompybullet_amd import VecPlayEnv
+    assert isinstance(inspect.getattr_static(VecPlayEnv, 'wrench_names'), property)
+    assert list(inspect.signature(VecPlayEnv.get_wrench).parameters) == ['self']
+    p = inspect.signature(VecPlayEnv.set_wrench).parameters
+    assert list(p) == ['self', 'wrench', 'mask'] and p['mask'].default is None and p['wrench'].default is inspect.Parameter.empty
+    p = inspect.signature(VecPlayEnv.push).parameters
+    assert list(p) == ['self', 'body', 'force', 'torque', 'mask']
+    assert all(p[k].default is None for k in ('force', 'torque', 'mask'))
+
+
+@pytest.mark.parametrize('kind', KINDS)
+def test_wrench_names_follow_the_bake(kind):
+    """per model: n_arm + n_free + n_j1 distinct names in that order; arm links by Bullet link index; free bodies exactly dynamics_names' mass columns;
+    every name that dynamics_names also uses (a link's, a scene body's friction column) means the same body"""
+    from roboticsplayroompybullet_amd.vec_env import dynamics_names, wrench_names
+    mdl = next(m for m in json.load(open(os.path.join(REPO, 'roboticsplayroompybullet_amd', 'assets', 'models.json')))['models'] if m['kind'] == kind)
+    names = wrench_names(kind)
+    na, nf, nj = mdl['n_arm'], len(mdl['free']), len(mdl['joint1'])
+    assert len(names) == na + nf + nj and len(set(names)) == len(names)
+    assert names[:na] == tuple('link%d' % a['bullet_index'] for a in mdl['arm'])
+    dn = dynamics_names(kind)
+    assert names[na:na + nf] == dn['mass']
+    # a friction column of the same name sits on colliders of the same body (body numbers: 1 + arm dof, then free bodies, then scene joints)
+    for b, name in enumerate(names):
+        if name in dn['friction']:
+            o = dn['friction'].index(name)
+            bodies = {c['body'] for c in mdl['col'] if c['obj'] == o}
+            assert bodies == {1 + b}, (kind, name, bodies)
+    # and every moving body with colliders whose object has a name of its own is called by it
+    for c in mdl['col']:
+        if c['body'] > na:
+            assert names[c['body'] - 1] == dn['friction'][c['obj']], (kind, c['body'])
+    if kind in ('U', 'V', 'W'):
+        assert names[na] == 'block' and 'drawer' in names[na:na + nf] and names[na + nf:] == ('door', 'button', 'dial')
+    if kind == 'P':
+        assert names[na:] == ('block',)
+
+
+def test_host_values_are_checked():
+    import torch
+    from roboticsplayroompybullet_amd.vec_env import check_wrench_values
+    assert check_wrench_values([[0.0, -1.5, 2.0, 0.0, 0.0, 0.0]]).tolist() == [[0.0, -1.5, 2.0, 0.0, 0.0, 0.0]]
+    assert check_wrench_values(np.zeros((3, 4, 6))).dtype == torch.float32
+    for bad in ([math.nan] * 6, [0.0, math.inf, 0.0, 0.0, 0.0, 0.0], np.array([[-math.inf] * 6]), torch.tensor([0.0, math.nan])):
+        with pytest.raises(ValueError):
+            check_wrench_values(bad)
