@@ -304,6 +304,22 @@ int rp_get_wrench_dims(rp_handle h, int32_t* n_arm, int32_t* n_free, int32_t* n_
 int rp_set_wrench(rp_handle h, const float* wrench, int32_t rows, const uint8_t* mask, void* stream);
 int rp_get_wrench(rp_handle h, float* wrench /* [N, n_body, 6] */, void* stream);
 
+/* Per-env gravity and arm-motor gain / strength (a mis-levelled table, an unknown payload, a softer or weaker actuator): every env has a float32 device row
+ * act [N, 3 + 2 * n_arm] = gravity[3] (m/s^2, world coordinates), motor_gain[n_arm], motor_strength[n_arm] (both dimensionless, dof order: the arm part of
+ * rp_get_wrench's bodies).  The gravity vector stands where (0, 0, -9.8) stood: the arm's base acceleration is -g, a free body's linear velocity gains dt g, a
+ * prismatic scene joint dt (axis . g).  An arm motor row asks for the velocity (0.1 * gain_i) (target_i - q_i) / dt and is bounded by -/+ (max impulse_i * strength_i),
+ * max impulse_i being what the action wrote into the state record (the record keeps that value).  Scene-joint motors, the Panda's finger gear row and the joint-limit
+ * rows do not read the table.  The values act from the next substep that builds rows (rp_step in every pipeline, the settle substeps of rp_reset, rp_step_autoreset's
+ * resets).  They are parameters, not state: rp_create writes (0, 0, -9.8), ones and ones, no reset changes them and rp_get_state / rp_set_state do not carry them.
+ * With those defaults every result is bit for bit what it is without a table.  Env indices are the handle's own (0 .. N-1). */
+int rp_get_actuation_dims(rp_handle h, int32_t* n_arm);
+/* gravity [rows, 3], motor_gain [rows, n_arm], motor_strength [rows, n_arm], rows = 1 (broadcast) or N, into every env whose mask byte is non-zero (mask NULL = all).
+ * A NULL array leaves that parameter as it is; all three NULL: RP_ERR_ARG.  rows not 1 or N: RP_ERR_ARG.  Enqueued on `stream`; no host wait.  The library does not
+ * range-check device values (VecPlayEnv checks host values: |g| <= 50 per component, 0 <= gain <= 10, 0 <= strength <= 10). */
+int rp_set_actuation(rp_handle h, const float* gravity, const float* motor_gain, const float* motor_strength, int32_t rows, const uint8_t* mask, void* stream);
+int rp_get_actuation(rp_handle h, float* gravity /* [N, 3] or NULL */, float* motor_gain /* [N, n_arm] or NULL */, float* motor_strength /* [N, n_arm] or NULL */,
+                     void* stream);
+
 int rp_get_timers(rp_handle h, rp_timers* t);
 /* on = number of rp_step calls to keep per-launch timings for (a ring); 0 disables */
 int rp_enable_timers(rp_handle h, int32_t on);

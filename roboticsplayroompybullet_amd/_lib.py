@@ -79,7 +79,8 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_compute_reward', 'rp_compute_reward_sparse', 'rp_state_bytes', 'rp_get_state', 'rp_set_state', 'rp_get_timers', 'rp_enable_timers',
            'rp_last_error', 'rp_version', 'rp_default_camera', 'rp_camera_from_yaw_pitch_roll', 'rp_render', 'rp_render_ex', 'rp_ray_test',
            'rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset', 'rp_set_reset_table', 'rp_get_reset_rows',
-           'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench']
+           'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench',
+           'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
                  'rp_debug_autoreset_shape']
@@ -126,6 +127,9 @@ def load(wide=False):
     lib.rp_get_wrench_dims.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.rp_set_wrench.argtypes = [vp, vp, C.c_int32, vp, vp]
     lib.rp_get_wrench.argtypes = [vp, vp, vp]
+    lib.rp_get_actuation_dims.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.rp_set_actuation.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp]
+    lib.rp_get_actuation.argtypes = [vp, vp, vp, vp, vp]
     lib.rp_compute_reward.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
     lib.rp_compute_reward_sparse.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
     lib.rp_state_bytes.argtypes = [vp]

@@ -114,6 +114,10 @@ typedef struct DevModel {
    * bodies, scene-joint bodies) a world force through its centre of mass and a world torque; arm_dynamics / unconstrained_velocities read the entries of the bodies
    * whose dofs their lanes own (ld_wrench) */
   const float* wrench;
+  /* per-env actuation (rp_set_actuation): [N][3 + 2 * n_arm], device memory owned by the handle, filled by rp_create with (0, 0, -9.8), ones, ones.  Row = the env's
+   * gravity vector (world), then a gain and a strength factor per arm motor in dof order; arm_dynamics / unconstrained_velocities read the gravity, build_small_rows
+   * the two factors of its dof (ld_gravity, ld_motor_gain, ld_motor_strength; k_solve2's motor-row rebuild gets them through the pending rows' bound slots) */
+  const float* act;
   /* convex-hull vertices of the arm links' collision meshes (generated/rp_hullverts_gen.h): device pointer to the arm's table (x, y, z, 0 in the owning
    * body's frame), per collider the first vertex and the count (0 = no hull).  rp_create uploads the table and sets the pointer. */
   const float* hullv;

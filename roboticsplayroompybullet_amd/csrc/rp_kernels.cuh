@@ -472,6 +472,12 @@ __device__ __forceinline__ V3 ld_wrench(const DevModel* m, int env, int body, in
   return ld3(m->wrench + ((size_t)env * (m->nbody - 1) + body) * 6 + 3 * half);
 }
 __device__ __forceinline__ bool wrench_on(V3 w) { return w.x != 0.f || w.y != 0.f || w.z != 0.f; }
+/* the per-env actuation table (DevModel.act, rp_set_actuation): the env's gravity vector (world), and the gain / strength factor of arm motor `dof`.  Read straight from
+ * global memory by the lane that needs it, like the wrench; env = the env's own index.  With the row rp_create writes - (0, 0, -9.8), 1, 1 - every result keeps its bits:
+ * dt * g.z rounds as the folded constant dt * -9.8f did, K_KP * 1 and mx * 1 are exact, and every x or y gravity term stands behind a != 0.f test (as wrench_on()) */
+__device__ __forceinline__ V3 ld_gravity(const DevModel* m, int env) { return ld3(m->act + (size_t)env * (3 + 2 * m->n_arm)); }
+__device__ __forceinline__ float ld_motor_gain(const DevModel* m, int env, int dof) { return m->act[(size_t)env * (3 + 2 * m->n_arm) + 3 + dof]; }
+__device__ __forceinline__ float ld_motor_strength(const DevModel* m, int env, int dof) { return m->act[(size_t)env * (3 + 2 * m->n_arm) + 3 + m->n_arm + dof]; }
 template <class LDS>
 __device__ __forceinline__ Xf collider_xf(const DevModel* m, const LDS& L, int c) {
   int b = m->col_body[c];
@@ -1941,6 +1947,7 @@ __device__ __forceinline__ void arm_dynamics(const DevModel* m, LDS& L, int lane
   V3 O = ld3(L.O);
   V3 wf = mk3(0, 0, 0), wt = mk3(0, 0, 0);      /* the env's wrench on link `lane` (asked for here, needed where the bias forces are built) */
   if (lane < n) { wf = ld_wrench(m, env, lane, 0); wt = ld_wrench(m, env, lane, 1); }
+  const V3 grav = ld_gravity(m, env);      /* the env's gravity (likewise) */
   if (lane < n) {      /* own spatial inertia about O: (m, h = m c, Ibar = R Ic R^T - m [c]x^2) */
     M3 R = ldm3(&L.xR[9 * (1 + lane)]);
     V3 c = ld3(&L.xp[3 * (1 + lane)]) + mulv(R, ld3(m->arm_com[lane])) - O;
@@ -1989,7 +1996,9 @@ __device__ __forceinline__ void arm_dynamics(const DevModel* m, LDS& L, int lane
   if (lane < n) {      /* bias force of each body: f = I a_bias + v x* (I v), a_bias = -g + sum of ancestors' c */
     uint32_t anc = m->arm_anc[lane];
     V6 a = zero6();
-    a.l.z = -K_GRAVITY;
+    a.l.z = -grav.z;
+    if (grav.x != 0.f) a.l.x = -grav.x;
+    if (grav.y != 0.f) a.l.y = -grav.y;
     for (int j = 0; j < n; j++) { V6 cj = ld6(&L.csp[6 * j]); bool on = (anc >> j) & 1u; a.a = a.a + (on ? cj.a : mk3(0, 0, 0)); a.l = a.l + (on ? cj.l : mk3(0, 0, 0)); }
     V6 v = ld6(&L.vsp[6 * lane]);
     const float* I = &L.inert[10 * lane];
@@ -2060,6 +2069,7 @@ __device__ __forceinline__ void unconstrained_velocities(const DevModel* m, LDS&
   V3 wv = mk3(0, 0, 0);      /* what this lane's dof feels of the env's wrench: a free body's force (linear dofs) or torque (angular), a scene joint's force (prismatic) or torque */
   if (lane >= n && lane < n + 6 * m->n_free) wv = ld_wrench(m, env, n + (lane - n) / 6, (lane - n) % 6 >= 3);
   else if (lane >= n && lane < m->nv) wv = ld_wrench(m, env, lane - 5 * m->n_free, m->j1_type[lane - n - 6 * m->n_free] != 1);
+  const V3 grav = ld_gravity(m, env);      /* the env's gravity: a free body's linear dofs and the prismatic scene joints feel it */
   if (lane < n) {
     float qdd = 0.f;
     for (int k = 0; k < n; k++) qdd -= L.Minv[lane * 12 + k] * L.tau[k];
@@ -2070,7 +2080,8 @@ __device__ __forceinline__ void unconstrained_velocities(const DevModel* m, LDS&
     if (c < 3) {
       V3 v = ld3(f + 7);
       float vn = norm(v);
-      vs = comp(v, c) + K_DT * (-(K_LIN_DAMP + K_LIN_DAMP * vn) * comp(v, c)) + (c == 2 ? K_DT * K_GRAVITY : 0.f);
+      vs = comp(v, c) + K_DT * (-(K_LIN_DAMP + K_LIN_DAMP * vn) * comp(v, c)) + (c == 2 ? K_DT * grav.z : 0.f);
+      if (c < 2 && comp(grav, c) != 0.f) vs += K_DT * comp(grav, c);
       if (comp(wv, c) != 0.f) vs += K_DT * comp(wv, c) / L.dmass[k];
     } else if (!m->free_rot_locked[k]) {
       M3 R = ldm3(&L.xR[9 * (1 + n + k)]);
@@ -2094,7 +2105,8 @@ __device__ __forceinline__ void unconstrained_velocities(const DevModel* m, LDS&
     if (m->j1_type[k] == 1) {
       M3 R = ldm3(&L.xR[9 * (1 + n + m->n_free + k)]);
       V3 a = mulv(R, ld3(m->j1_axis[k]));
-      vs = qd + K_DT * K_GRAVITY * a.z;
+      vs = qd + K_DT * grav.z * a.z;
+      if (grav.x != 0.f || grav.y != 0.f) vs += K_DT * __fmaf_rn(a.y, grav.y, a.x * grav.x);
     } else {
       vs = qd + K_DT * (-(K_ANG_DAMP + K_ANG_DAMP * fabsf(qd)) * qd);
     }
@@ -2138,7 +2150,7 @@ __device__ __forceinline__ void put_srow(LDS& L, int r, int type, int dofA, floa
  * (btMultiBodyJointLimitConstraint::createConstraintRows).  Same rule as the oracle's build_rows (RPO_RULE_ORDER | RPO_RULE_LIMIT) and the frozen
  * reference step (rp_bullet_ref.c RPB_ORDER, RPB_LIMIT).  Returns the number of small rows (wave-uniform). */
 template <class LDS>
-__device__ __forceinline__ int build_small_rows(const DevModel* m, LDS& L, int lane) {
+__device__ __forceinline__ int build_small_rows(const DevModel* m, LDS& L, int lane, int env, bool pending = false) {
   int n = m->n_arm, nr = 0;
   if (lane < m->n_j1) {  /* scene joint motors */
     int d = dof_j1(m, lane);
@@ -2167,12 +2179,15 @@ __device__ __forceinline__ int build_small_rows(const DevModel* m, LDS& L, int l
     }
     nr += __popcll(mask);
   }
-  if (lane < n) {        /* arm motors (btMultiBodyJointMotor) */
+  if (lane < n) {        /* arm motors (btMultiBodyJointMotor), the gain and the bound scaled by the env's factors (rp_set_actuation) */
     float dinv = 1.f / L.Minv[lane * 12 + lane];
     float mode = L.st[ST_MMODE + lane];
-    float des = mode != 0.f ? K_KP * (L.st[ST_MTARGET + lane] - L.st[ST_Q + lane]) / K_DT : 0.f;
-    float mx = L.st[ST_MMAXIMP + lane];
-    put_srow(L, nr + lane, SR_UNIT, lane, 1.f, (des - L.vstar[lane]) * dinv, dinv, -mx, mx, 0);
+    float kg = ld_motor_gain(m, env, lane), ks = ld_motor_strength(m, env, lane);
+    float des = mode != 0.f ? K_KP * kg * (L.st[ST_MTARGET + lane] - L.st[ST_Q + lane]) / K_DT : 0.f;
+    float mx = L.st[ST_MMAXIMP + lane] * ks;
+    /* pending (k_action_prep: the action is still being computed, k_solve2 rebuilds this row from the record): the bounds' places carry the env's two factors to it,
+     * so that the solver reads no table */
+    put_srow(L, nr + lane, SR_UNIT, lane, 1.f, (des - L.vstar[lane]) * dinv, dinv, pending ? kg : -mx, pending ? ks : mx, 0);
   }
   nr += n;
   if (m->arm_type == RP_ARM_PANDA) {   /* finger gear: qd_a + ratio qd_b -> 0 (environments.py:400-405) */
@@ -2470,7 +2485,7 @@ __device__ void substep(const DevModel* m, EnvLds& L, int lane, int env) {
   int ncon = collide(m, L, lane, env);
   arm_dynamics(m, L, lane, env);
   unconstrained_velocities(m, L, lane, env);
-  int nsmall = build_small_rows(m, L, lane);
+  int nsmall = build_small_rows(m, L, lane, env);
   const int nt = tors_list(m, L, lane, ncon);
   WSYNC();
   contact_rows(m, L, lane, 0, ncon, nt);
@@ -3413,6 +3428,31 @@ __global__ void k_get_wrench(const float* __restrict__ tab, float* __restrict__ 
   if (i < total) dst[i] = tab[i];
 }
 
+/* per-env actuation table (rp_set_actuation / rp_get_actuation): thread per table entry; the row is gravity[3], motor_gain[na], motor_strength[na].  Sources [rows][3] /
+ * [rows][na] / [rows][na], rows 1 = every env the same row, a nullptr source leaves its columns alone; only envs whose mask byte is non-zero (mask nullptr: all) */
+__global__ void k_set_actuation(float* __restrict__ tab, const float* __restrict__ gr, const float* __restrict__ gn, const float* __restrict__ sg, int rows,
+                                const uint8_t* __restrict__ mask, int N, int na) {
+  const int W = 3 + 2 * na;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * W) return;
+  const size_t env = i / W, r = rows == 1 ? 0 : env;
+  const int k = (int)(i % W);
+  if (mask && !mask[env]) return;
+  if (k < 3) { if (gr) tab[i] = gr[r * 3 + k]; }
+  else if (k < 3 + na) { if (gn) tab[i] = gn[r * na + (k - 3)]; }
+  else if (sg) tab[i] = sg[r * na + (k - 3 - na)];
+}
+__global__ void k_get_actuation(const float* __restrict__ tab, float* __restrict__ gr, float* __restrict__ gn, float* __restrict__ sg, int N, int na) {
+  const int W = 3 + 2 * na;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * W) return;
+  const size_t env = i / W;
+  const int k = (int)(i % W);
+  if (k < 3) { if (gr) gr[env * 3 + k] = tab[i]; }
+  else if (k < 3 + na) { if (gn) gn[env * na + (k - 3)] = tab[i]; }
+  else if (sg) sg[env * na + (k - 3 - na)] = tab[i];
+}
+
 /* ------------------------------------------------------------------ split pipeline for rp_step
  * The fused substep() above needs > 256 VGPRs in its cold phases (IK, narrowphase, row build) although the hot PGS
  * loop needs ~60, so rp_step runs right-sized kernels instead:
@@ -3594,7 +3634,7 @@ __device__ __forceinline__ void prep2_core(PrepLds& L, const DevModel* __restric
     arm_dynamics(m, L, lane, cenv);
     unconstrained_velocities(m, L, lane, cenv);
     PCLK(3)
-    int nsmall = build_small_rows(m, L, lane);
+    int nsmall = build_small_rows(m, L, lane, cenv, (prep_flags & 2) != 0);
     nsmall = uni(nsmall);
     for (int i = lane; i < AOUT_FLOATS; i += 64) L.aout[i] = 0.f;
     if (lane < 2) L.amask[lane] = 0u;
@@ -3762,7 +3802,7 @@ __global__ void __launch_bounds__(PREP_THREADS, RP_PREP_WAVES) k_action_prep(con
     __builtin_amdgcn_s_setprio(3);
     action_body(m, state, action, target_poses, env0, N, member, blockIdx.x);
   }
-  else prep2_body(m, state, ws, env0, N, sort_cnt, sort_cnt_next, sort_slot, pair_env, member, blockIdx.x - nab, nullptr, hv_cnt, hv_cnt_next, hv_list, prep_flags);
+  else prep2_body(m, state, ws, env0, N, sort_cnt, sort_cnt_next, sort_slot, pair_env, member, blockIdx.x - nab, nullptr, hv_cnt, hv_cnt_next, hv_list, prep_flags | 2);      /* bit 1: the motor rows are pending (build_small_rows) */
 }
 
 
@@ -3957,8 +3997,9 @@ __device__ __forceinline__ void solve4_body(const DevModel* __restrict__ m, floa
     PU.rhs = ldz(&wa[112 + ia], arm_lane); PU.lo = ldz(&wa[128 + ia], arm_lane); PU.hi = ldz(&wa[144 + ia], arm_lane);
     if (debug_flags & 2) {      /* first substep after k_action_prep: the motor rows from the record's fresh targets (build_small_rows' formula) */
       const float* r = state + (size_t)(valid ? env : 0) * RP_REC_FLOATS;
-      const float mode = r[ST_MMODE + ia], tgt = r[ST_MTARGET + ia], mx = r[ST_MMAXIMP + ia], qi = r[ST_Q + ia];
-      const float des = mode != 0.f ? K_KP * (tgt - qi) / K_DT : 0.f;
+      /* (k_action_prep left the env's motor gain and strength factors in the bounds' places: build_small_rows, pending) */
+      const float mode = r[ST_MMODE + ia], tgt = r[ST_MTARGET + ia], mx = r[ST_MMAXIMP + ia] * X0.hi, qi = r[ST_Q + ia];
+      const float des = mode != 0.f ? K_KP * X0.lo * (tgt - qi) / K_DT : 0.f;
       const float rhs = (des - vstar) * dinvX;
       if (arm_lane) { X0.rhs = rhs; X0.lo = -mx; X0.hi = mx; }
     }
@@ -4452,8 +4493,9 @@ __device__ __forceinline__ void heavy_solve(const DevModel* __restrict__ m, floa
   }
   if (debug_flags & RP_DBG_MOTOR) {      /* first substep after k_action_prep: the motor rows from the record's fresh targets (build_small_rows' formula) */
     const float* r = st_lds ? st_lds : state + (size_t)env * RP_REC_FLOATS;
-    const float mode = r[ST_MMODE + ia], tgt = r[ST_MTARGET + ia], mx = r[ST_MMAXIMP + ia], qi = r[ST_Q + ia];
-    const float des = mode != 0.f ? K_KP * (tgt - qi) / K_DT : 0.f;
+    /* (k_action_prep left the env's motor gain and strength factors in the bounds' places: build_small_rows, pending) */
+    const float mode = r[ST_MMODE + ia], tgt = r[ST_MTARGET + ia], mx = r[ST_MMAXIMP + ia] * P0.hi, qi = r[ST_Q + ia];
+    const float des = mode != 0.f ? K_KP * P0.lo * (tgt - qi) / K_DT : 0.f;
     const float rhs = (des - vstar_a) * jd;
     if (arm_lane) { rhs0 = rhs; P0.lo = -mx; P0.hi = mx; }
   }
@@ -4840,8 +4882,9 @@ __device__ __forceinline__ void super_solve(const DevModel* __restrict__ m, floa
     float* sr = &L.srow[8 * lane];
     if (__float_as_int(sr[0]) == SR_UNIT) {
       const int dA = __float_as_int(sr[1]);
-      const float mode = L.st[ST_MMODE + dA], tgt = L.st[ST_MTARGET + dA], mx = L.st[ST_MMAXIMP + dA], qi = L.st[ST_Q + dA];
-      const float des = mode != 0.f ? K_KP * (tgt - qi) / K_DT : 0.f;
+      /* (k_action_prep left the env's motor gain and strength factors in the bounds' places: build_small_rows, pending) */
+      const float mode = L.st[ST_MMODE + dA], tgt = L.st[ST_MTARGET + dA], mx = L.st[ST_MMAXIMP + dA] * sr[6], qi = L.st[ST_Q + dA];
+      const float des = mode != 0.f ? K_KP * sr[5] * (tgt - qi) / K_DT : 0.f;
       sr[3] = (des - L.vstar[dA]) * sr[4]; sr[5] = -mx; sr[6] = mx;
     }
   }
@@ -5406,7 +5449,7 @@ __global__ void __launch_bounds__(64) k_debug_substep(const DevModel* __restrict
     for (int i = 0; i < 32; i++) dbg[480 + i] = L.vstar[i];
     for (int i = 0; i < n; i++) dbg[512 + i] = L.tau[i];
   }
-  int nsmall = build_small_rows(m, L, lane);
+  int nsmall = build_small_rows(m, L, lane, env);
   const int nt = tors_list(m, L, lane, ncon);
   WSYNC();
   contact_rows(m, L, lane, 0, ncon, nt);

@@ -30,6 +30,7 @@ struct rp_sim {
   float* pmcache;          /* the contact caches, [N][PMC_FLOATS] (DevModel.pmcache points here); nullptr under RP_CFG_STATELESS_CONTACTS */
   float* dyn;              /* the per-env dynamics table, [N][n_obj + n_free] (DevModel.dyn points here) */
   float* wrench;           /* the per-env wrench table, [N][n_arm + n_free + n_j1][6] (DevModel.wrench points here) */
+  float* act;              /* the per-env actuation table, [N][3 + 2 n_arm]: gravity, motor gains, motor strengths (DevModel.act points here) */
   int* sort_cnt;           /* [2][RP_MAX_GROUPS][SORT_BINS] load-class histograms for pairing envs in k_solve2 (double-buffered) */
   int* sort_slot;          /* [N] per env: (bin << 16) | rank inside the bin, from the latest k_solve2 */
   int* pair_env;           /* [N] per group range: env ids sorted by load class, heaviest first (k_solve2 pairs neighbours) */
@@ -107,14 +108,14 @@ extern "C" {
 #define RP_BUILD_ID "unversioned"
 #endif
 #ifdef RP_WIDE
-const char* rp_version(void) { return "rp_playroom 0.5.1 (gfx950, wide build: two-object play ids) build " RP_BUILD_ID; }
+const char* rp_version(void) { return "rp_playroom 0.5.2 (gfx950, wide build: two-object play ids) build " RP_BUILD_ID; }
 #else
-const char* rp_version(void) { return "rp_playroom 0.5.1 (gfx950) build " RP_BUILD_ID; }
+const char* rp_version(void) { return "rp_playroom 0.5.2 (gfx950) build " RP_BUILD_ID; }
 #endif
 
 static void destroy_handle(rp_sim* h) {        /* frees whatever a (possibly partial) handle owns; hipFree(nullptr) etc. are no-ops */
   if (!h) return;
-  hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dyn); hipFree(h->wrench); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
+  hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dyn); hipFree(h->wrench); hipFree(h->act); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
   hipFree(h->rc_tab); hipFree(h->rc_cnt); hipFree(h->rc_ee);
   hipFree(h->ep_steps); hipFree(h->ar_list); hipFree(h->ar_ctl); hipFree(h->ar_pair);
   hipFree(h->rt_tab); hipFree(h->rt_cursor); hipFree(h->rt_env_row); hipFree(h->rt_wave_bal); hipFree(h->rt_wave_row);
@@ -313,6 +314,18 @@ int rp_create(const rp_config* cfg, rp_handle* out) {
     CREATE_CHK(hipMalloc((void**)&h->wrench, bytes));
     CREATE_CHK(hipMemset(h->wrench, 0, bytes));
     d->wrench = h->wrench;
+  }
+  {      /* the per-env actuation table, every row the constants the kernels had: gravity (0, 0, -9.8), motor gain 1, motor strength 1 */
+    const int na = d->n_arm, W = 3 + 2 * na;
+    float row[3 + 2 * RP_MAX_ARM];
+    row[0] = 0.f; row[1] = 0.f; row[2] = K_GRAVITY;
+    for (int i = 0; i < 2 * na; i++) row[3 + i] = 1.f;
+    CREATE_CHK(hipMalloc((void**)&h->act, (size_t)(N + 1) * W * sizeof(float)));      /* (+ one row behind the table: the default row, broadcast from there) */
+    const float* base = h->act + (size_t)N * W;
+    CREATE_CHK(hipMemcpy((void*)base, row, W * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_set_actuation, dim3((unsigned)(((size_t)N * W + 255) / 256)), dim3(256), 0, 0, h->act, base, base + 3, base + 3 + na, 1, (const uint8_t*)nullptr, N, na);
+    CREATE_CHK(hipGetLastError());
+    d->act = h->act;
   }
   CREATE_CHK(hipMemcpy(h->dev_model, &h->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
   CREATE_CHK(hipEventCreate(&h->ev0));
@@ -766,6 +779,36 @@ int rp_get_wrench(rp_handle h, float* wrench, void* stream) {
   DevGuard guard(h->cfg.device);
   const size_t total = (size_t)h->cfg.num_envs * 6 * (h->host_model.nbody - 1);
   hipLaunchKernelGGL(k_get_wrench, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->wrench, wrench, total);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+int rp_get_actuation_dims(rp_handle h, int32_t* n_arm) {
+  if (!h || !n_arm) return RP_ERR_ARG;
+  *n_arm = h->host_model.n_arm;
+  return RP_OK;
+}
+
+/* enqueued on `stream` like rp_set_dynamics: a step queued after it on the same stream runs under the new values from its first substep, one queued before it under the old ones */
+int rp_set_actuation(rp_handle h, const float* gravity, const float* motor_gain, const float* motor_strength, int32_t rows, const uint8_t* mask, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  const int N = h->cfg.num_envs, na = h->host_model.n_arm;
+  if (!gravity && !motor_gain && !motor_strength) { snprintf(h->err, 256, "rp_set_actuation: gravity, motor_gain and motor_strength are all NULL"); return RP_ERR_ARG; }
+  if (rows != 1 && rows != N) { snprintf(h->err, 256, "rp_set_actuation: rows = %d, expected 1 or num_envs = %d", rows, N); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const size_t total = (size_t)N * (3 + 2 * na);
+  hipLaunchKernelGGL(k_set_actuation, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->act, gravity, motor_gain, motor_strength, (int)rows, mask,
+                     N, na);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+int rp_get_actuation(rp_handle h, float* gravity, float* motor_gain, float* motor_strength, void* stream) {
+  if (!h || (!gravity && !motor_gain && !motor_strength)) { if (h) snprintf(h->err, 256, "rp_get_actuation: gravity, motor_gain and motor_strength are all NULL"); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const int N = h->cfg.num_envs, na = h->host_model.n_arm;
+  const size_t total = (size_t)N * (3 + 2 * na);
+  hipLaunchKernelGGL(k_get_actuation, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->act, gravity, motor_gain, motor_strength, N, na);
   HIPCHK(h, hipGetLastError());
   return RP_OK;
 }

@@ -98,6 +98,30 @@ def check_wrench_values(v):
     return t
 
 
+def actuation_names(model):
+    """{'gravity': ['x', 'y', 'z'], 'motor': the arm's dofs as wrench_names calls their links ('link7', in dof order)} of a baked model: the columns of
+    rp_get_actuation's gravity and of its motor_gain / motor_strength"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets', 'models.json')) as f:
+        mdl = next(m for m in json.load(f)['models'] if m['kind'] == model)
+    return {'gravity': ('x', 'y', 'z'), 'motor': tuple('link%d' % a['bullet_index'] for a in mdl['arm'])}
+
+
+ACTUATION_RANGES = {'gravity': (-50.0, 50.0), 'motor_gain': (0.0, 10.0), 'motor_strength': (0.0, 10.0)}
+
+
+def check_actuation_values(what, v):
+    """a host-side gravity / motor_gain / motor_strength value (sequence, numpy array, CPU tensor) as a float32 CPU tensor; finite and inside
+    ACTUATION_RANGES (|g| <= 50 per component; 0 <= gain <= 10, which keeps the motor's position gain 0.1 * gain <= 1; 0 <= strength <= 10),
+    ValueError otherwise"""
+    t = torch.as_tensor(v, dtype=torch.float32, device='cpu')
+    lo, hi = ACTUATION_RANGES[what]
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError('%s: values must be finite' % what)
+    if not bool(((t >= lo) & (t <= hi)).all()):
+        raise ValueError('%s: values must lie in [%g, %g]' % (what, lo, hi))
+    return t
+
+
 class VecPlayEnv:
     def __init__(self, env_id, num_envs, device=0, seed=0, env_offset=0, action_type=None, goal_range_low=None, goal_range_high=None,
                  obj_lower_bound=None, obj_upper_bound=None, env_range_high=None, sparse_rew_thresh=None, sparse=True,
@@ -478,6 +502,58 @@ class VecPlayEnv:
                 raise ValueError('push: %s has shape %s, expected [3] or [%d, 3]' % (('force', 'torque')[half], tuple(t.shape), self.num_envs))
             w[:, b, 3 * half:3 * half + 3] = t
         self.set_wrench(w, mask=mask)
+
+    @property
+    def actuation_names(self):
+        """{'gravity': ('x', 'y', 'z'), 'motor': a name per arm dof}: the columns of get_actuation / set_actuation"""
+        return actuation_names(MODEL_OF[self.env_id])
+
+    def _n_arm(self):
+        na = C.c_int32()
+        _lib.check(self.lib, self.h, self.lib.rp_get_actuation_dims(self.h, C.byref(na)), 'rp_get_actuation_dims')
+        return na.value
+
+    def get_actuation(self):
+        """{'gravity': [N, 3], 'motor_gain': [N, n_arm], 'motor_strength': [N, n_arm]} float32 device tensors: every env's gravity vector (m/s^2,
+        world) and the gain and strength factor of each arm motor in dof order (a fresh handle: (0, 0, -9.8), ones, ones)"""
+        na = self._n_arm()
+        g = torch.empty((self.num_envs, 3), dtype=torch.float32, device=self.device)
+        kp = torch.empty((self.num_envs, na), dtype=torch.float32, device=self.device)
+        st = torch.empty((self.num_envs, na), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib, self.h, self.lib.rp_get_actuation(self.h, C.c_void_p(g.data_ptr()), C.c_void_p(kp.data_ptr()), C.c_void_p(st.data_ptr()),
+                                                               self._stream()), 'rp_get_actuation')
+        return {'gravity': g, 'motor_gain': kp, 'motor_strength': st}
+
+    def set_actuation(self, gravity=None, motor_gain=None, motor_strength=None, mask=None):
+        """Per-env gravity vector ([N, 3] or [3]: every env the same) and / or a gain and a strength factor per arm motor ([N, n_arm] or [n_arm], dof
+        order: actuation_names['motor']) for the envs where mask [N] != 0 (None: all); None leaves that parameter as it is.  Gravity acts on the arm,
+        the free bodies and the prismatic scene joints; an arm motor asks for 0.1 * gain * (target - q) / dt and is bounded by strength times the
+        impulse the action gave it (strength 0: the motor is off).  The values act from the next step or reset substep on this stream, and no reset
+        changes them.  Host values (sequences, numpy, CPU tensors) are checked (|g| <= 50 per component, 0 <= gain <= 10, 0 <= strength <= 10,
+        finite); tensors on the env's device are passed through without a host read, so the call can sit in a device-side loop (e.g. mask=done)."""
+        if gravity is None and motor_gain is None and motor_strength is None:
+            raise ValueError('set_actuation: give gravity, motor_gain, motor_strength or several')
+        N, na = self.num_envs, self._n_arm()
+
+        def prep(what, v, k):
+            if v is None:
+                return None, 0
+            on_dev = isinstance(v, torch.Tensor) and v.device == self.device
+            t = v.to(dtype=torch.float32) if on_dev else check_actuation_values(what, v).to(self.device)
+            if t.dim() == 1 and t.shape[0] == k:
+                return t.contiguous(), 1
+            if t.dim() == 2 and t.shape == (N, k):
+                return t.contiguous(), N
+            raise ValueError('set_actuation: %s has shape %s, expected [%d] or [%d, %d]' % (what, tuple(t.shape), k, N, k))
+
+        parts = [prep('gravity', gravity, 3), prep('motor_gain', motor_gain, na), prep('motor_strength', motor_strength, na)]
+        rows = max(r for _, r in parts)      # one call, one row count: single rows are broadcast when another part has N
+        parts = [t.expand(N, -1).contiguous() if t is not None and r != rows else t for t, r in parts]
+        mask = self._mask('set_actuation', mask)
+        _lib.check(self.lib, self.h, self.lib.rp_set_actuation(self.h, *[C.c_void_p(t.data_ptr()) if t is not None else None for t in parts], rows,
+                                                               C.c_void_p(mask.data_ptr()) if mask is not None else None, self._stream()),
+                   'rp_set_actuation')
+        self._act_src = (parts, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
 
     def calc_state(self):
         self._flip_pack()
