@@ -320,6 +320,32 @@ int rp_set_actuation(rp_handle h, const float* gravity, const float* motor_gain,
 int rp_get_actuation(rp_handle h, float* gravity /* [N, 3] or NULL */, float* motor_gain /* [N, n_arm] or NULL */, float* motor_strength /* [N, n_arm] or NULL */,
                      void* stream);
 
+/* Per-env joint and body state by column (a drawer half open, a thrown block, an arm at a joint vector without IK; the reference's resetJointState,
+ * resetBasePositionAndOrientation, resetBaseVelocity and their getters, ENV:519-603): the kinematic words of the state record as two float32 tables, with
+ * n_arm, n_free, n_j1 of rp_get_wrench_dims,
+ *   pos [N, n_pos], n_pos = n_arm + 7 * n_free + n_j1: arm q[n_arm] (dof order), per free body x y z qx qy qz qw (record order), scene-joint q[n_j1]
+ *   vel [N, n_vel], n_vel = n_arm + 6 * n_free + n_j1: arm qd, per free body vx vy vz wx wy wz (world), scene-joint qd
+ * - the order of the oracle's rpo_get_state vector with positions and velocities split.  rp_set_kinematics writes exactly those words, verbatim (a quaternion is not
+ * normalised; VecPlayEnv checks host values), for every env whose mask byte is non-zero (mask NULL = all); rows = 1 (broadcast) or N; a NULL array leaves that half as it
+ * is.  Nothing else changes: motor mode / target / max impulse, goal, quaternion sign memory, RNG counter, status, episode counter and the dynamics, wrench and
+ * actuation tables stay.  The contact-cache row stays too, as rp_reset_to leaves it: the next substep's refresh drops the points beyond their breaking threshold.  With
+ * RP_KIN_CLEAR_CONTACTS the masked envs' cache rows are zeroed (a state without contact history); under RP_CFG_STATELESS_CONTACTS the flag does nothing.  Enqueued on
+ * `stream`; no host wait, no host read of device values.  Both arrays NULL, rows not 1 or N, unknown flag bits: RP_ERR_ARG. */
+enum rp_kin_flags { RP_KIN_CLEAR_CONTACTS = 1 };
+int rp_get_kinematics(rp_handle h, float* pos /* [N, n_pos] or NULL */, float* vel /* [N, n_vel] or NULL */, void* stream);
+int rp_set_kinematics(rp_handle h, const float* pos, const float* vel, int32_t rows, const uint8_t* mask, uint32_t flags, void* stream);
+
+/* Envs cloned on the device (CEM-MPC rollouts from one state, population-based training, particle resampling): every env e whose mask byte is non-zero (mask NULL = all)
+ * takes the whole state row of env src[e] (int32 [N], device pointer) AS IT WAS BEFORE THE CALL - the state record and, unless RP_CFG_STATELESS_CONTACTS, the
+ * contact-cache row: what rp_get_state, a gather of the rows by src and rp_set_state would leave.  Gather semantics: any src is served (permutations, cycles,
+ * many-to-one, identity).  With RP_COPY_EPISODE_STEPS the env also takes that env's episode counter.  An env whose src[e] is outside [0, N) is left unchanged.  The
+ * dynamics, wrench and actuation tables, the reset table and its cursor are not copied.  Staging: every row is first copied into a buffer of the handle's own, one extra
+ * copy of the rows (rp_state_bytes + 4 bytes per env), allocated by the first call and freed by rp_destroy - not the row workspace, so rp_debug_row_counts still sees the
+ * latest substep.  Two launches on `stream`; no host wait.  The call reads and writes the state rows and shares the one staging buffer: do not overlap it with rp_step,
+ * rp_reset or another rp_copy_envs of the same handle on another stream.  src NULL, unknown flag bits: RP_ERR_ARG. */
+enum rp_copy_flags { RP_COPY_EPISODE_STEPS = 1 };
+int rp_copy_envs(rp_handle h, const int32_t* src /* [N] */, const uint8_t* mask, uint32_t flags, void* stream);
+
 int rp_get_timers(rp_handle h, rp_timers* t);
 /* on = number of rp_step calls to keep per-launch timings for (a ring); 0 disables */
 int rp_enable_timers(rp_handle h, int32_t on);

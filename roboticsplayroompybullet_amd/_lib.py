@@ -48,6 +48,9 @@ CFG_GOAL_RANGE, CFG_OBJ_RANGE, CFG_ENV_RANGE, CFG_REW_THRESH, CFG_DENSE_REWARD, 
 AR_TIME_LIMIT, AR_FAULT, AR_SUCCESS = 1, 2, 4
 # the bits of rp_step_autoreset's done[] (done_reason): time limit, end_mask, fault (status & 3), is_success
 DONE_TIME_LIMIT, DONE_END_MASK, DONE_FAULT, DONE_SUCCESS = 1, 2, 4, 8
+# rp_kin_flags / rp_copy_flags (include/rp_playroom.h)
+KIN_CLEAR_CONTACTS = 1
+COPY_EPISODE_STEPS = 1
 ACTION_TYPE_CODES = {'absolute_rpy': 0, 'relative_rpy': 1, 'absolute_quat': 2, 'relative_quat': 3, 'absolute_joints': 4, 'relative_joints': 5}
 
 
@@ -80,7 +83,7 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_last_error', 'rp_version', 'rp_default_camera', 'rp_camera_from_yaw_pitch_roll', 'rp_render', 'rp_render_ex', 'rp_ray_test',
            'rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset', 'rp_set_reset_table', 'rp_get_reset_rows',
            'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench',
-           'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation']
+           'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
                  'rp_debug_autoreset_shape']
@@ -130,6 +133,9 @@ def load(wide=False):
     lib.rp_get_actuation_dims.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.rp_set_actuation.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp]
     lib.rp_get_actuation.argtypes = [vp, vp, vp, vp, vp]
+    lib.rp_get_kinematics.argtypes = [vp, vp, vp, vp]
+    lib.rp_set_kinematics.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_uint32, vp]
+    lib.rp_copy_envs.argtypes = [vp, vp, vp, C.c_uint32, vp]
     lib.rp_compute_reward.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
     lib.rp_compute_reward_sparse.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
     lib.rp_state_bytes.argtypes = [vp]

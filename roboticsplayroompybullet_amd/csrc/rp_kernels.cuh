@@ -3428,6 +3428,75 @@ __global__ void k_get_wrench(const float* __restrict__ tab, float* __restrict__ 
   if (i < total) dst[i] = tab[i];
 }
 
+/* per-env kinematics (rp_set_kinematics / rp_get_kinematics): thread per word.  A pos row is arm q[na], per free body x y z qx qy qz qw, scene-joint q[nj]; a vel row
+ * arm qd[na], per free body vx vy vz wx wy wz, scene-joint qd[nj]: the oracle's rpo_get_state order with positions and velocities split.  kin_pos_word / kin_vel_word
+ * give column k's place in the state record */
+__device__ __forceinline__ int kin_pos_word(int k, int na, int nf) {
+  if (k < na) return ST_Q + k;
+  k -= na;
+  if (k < 7 * nf) return ST_FREE + 13 * (k / 7) + k % 7;
+  return ST_JQ + (k - 7 * nf);
+}
+__device__ __forceinline__ int kin_vel_word(int k, int na, int nf) {
+  if (k < na) return ST_QD + k;
+  k -= na;
+  if (k < 6 * nf) return ST_FREE + 13 * (k / 6) + 7 + k % 6;
+  return ST_JQD + (k - 6 * nf);
+}
+/* pos [rows][np] / vel [rows][nv] (nullptr: leave that half), rows 1 = every env the same row; only envs whose mask byte is non-zero (mask nullptr: all).  A row of the
+ * grid is np + nv + nclr threads: the last nclr (PMC_FLOATS with RP_KIN_CLEAR_CONTACTS and a cache, else 0) zero the env's contact-cache row */
+__global__ void k_set_kinematics(float* __restrict__ rec, float* __restrict__ cache, const float* __restrict__ pos, const float* __restrict__ vel, int rows,
+                                 const uint8_t* __restrict__ mask, int N, int na, int nf, int nj, int nclr) {
+  const int np = na + 7 * nf + nj, nv = na + 6 * nf + nj;
+  const size_t W = (size_t)(np + nv + nclr);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * W) return;
+  const size_t env = i / W, r = rows == 1 ? 0 : env;
+  const int k = (int)(i % W);
+  if (mask && !mask[env]) return;
+  if (k < np) { if (pos) rec[env * RP_REC_FLOATS + kin_pos_word(k, na, nf)] = pos[r * np + k]; }
+  else if (k < np + nv) { if (vel) rec[env * RP_REC_FLOATS + kin_vel_word(k - np, na, nf)] = vel[r * nv + (k - np)]; }
+  else cache[env * PMC_FLOATS + (k - np - nv)] = 0.f;
+}
+__global__ void k_get_kinematics(const float* __restrict__ rec, float* __restrict__ pos, float* __restrict__ vel, int N, int na, int nf, int nj) {
+  const int np = na + 7 * nf + nj, nv = na + 6 * nf + nj;
+  const size_t W = (size_t)(np + nv);
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * W) return;
+  const size_t env = i / W;
+  const int k = (int)(i % W);
+  if (k < np) { if (pos) pos[env * np + k] = rec[env * RP_REC_FLOATS + kin_pos_word(k, na, nf)]; }
+  else if (vel) vel[env * nv + (k - np)] = rec[env * RP_REC_FLOATS + kin_vel_word(k - np, na, nf)];
+}
+
+/* rp_copy_envs in two launches on one stream, thread per 16 bytes of a row (record, then nc4 float4 of the contact cache; 0 under RP_CFG_STATELESS_CONTACTS):
+ * k_copy_envs_stage copies every env's row and episode counter into the staging buffer (stage [N][RP_REC_FLOATS / 4 + nc4] float4, steps_stage [N]), k_copy_envs_gather
+ * then gives every masked env e with 0 <= src[e] < N the staged row of env src[e] - so every row read is the row as it was before the call, whatever src is - and,
+ * with ep_steps, that env's staged counter.  An env whose src is outside [0, N) keeps its row. */
+static_assert(RP_REC_FLOATS % 4 == 0 && PMC_FLOATS % 4 == 0, "k_copy_envs_*: rows move as float4");
+__global__ void k_copy_envs_stage(float4* __restrict__ stage, int* __restrict__ steps_stage, const float4* __restrict__ rec, const float4* __restrict__ cache,
+                                  const int* __restrict__ ep_steps, int N, int nc4) {
+  const size_t R4 = RP_REC_FLOATS / 4, W = R4 + (size_t)nc4;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * W) return;
+  const size_t env = i / W, k = i % W;
+  stage[i] = k < R4 ? rec[env * R4 + k] : cache[env * nc4 + (k - R4)];
+  if (k == 0) steps_stage[env] = ep_steps[env];
+}
+__global__ void k_copy_envs_gather(float4* __restrict__ rec, float4* __restrict__ cache, int* __restrict__ ep_steps, const float4* __restrict__ stage,
+                                   const int* __restrict__ steps_stage, const int* __restrict__ src, const uint8_t* __restrict__ mask, int N, int nc4, int copy_steps) {
+  const size_t R4 = RP_REC_FLOATS / 4, W = R4 + (size_t)nc4;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * W) return;
+  const size_t env = i / W, k = i % W;
+  if (mask && !mask[env]) return;
+  const int s = src[env];
+  if (s < 0 || s >= N) return;
+  const float4 v = stage[(size_t)s * W + k];
+  if (k < R4) rec[env * R4 + k] = v; else cache[env * nc4 + (k - R4)] = v;
+  if (k == 0 && copy_steps) ep_steps[env] = steps_stage[s];
+}
+
 /* per-env actuation table (rp_set_actuation / rp_get_actuation): thread per table entry; the row is gravity[3], motor_gain[na], motor_strength[na].  Sources [rows][3] /
  * [rows][na] / [rows][na], rows 1 = every env the same row, a nullptr source leaves its columns alone; only envs whose mask byte is non-zero (mask nullptr: all) */
 __global__ void k_set_actuation(float* __restrict__ tab, const float* __restrict__ gr, const float* __restrict__ gn, const float* __restrict__ sg, int rows,

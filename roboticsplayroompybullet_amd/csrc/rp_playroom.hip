@@ -61,6 +61,7 @@ struct rp_sim {
   int* ep_steps; int* ar_list; int* ar_ctl; int* ar_pair;
   int ar_grid, ar_epb;     /* k_autoreset's grid (the blocks resident at once; RP_AUTORESET_BLOCKS overrides) and envs per block (RP_AUTORESET_EPB, 1 .. 4, default 1) */
   int32_t ar_max_steps; uint32_t ar_when;      /* rp_set_autoreset */
+  float* cp_stage;         /* rp_copy_envs: one staged copy of every state row, [N][RP_REC_FLOATS + (PMC_FLOATS)], and behind it the episode counters [N] (allocated at the first call) */
   /* rp_set_reset_table: the table [rt_rows, rt_n_o] (rt_rows = 0: none), the row cursor [1], each env's row of the latest autoreset step [N] (-1: none), the waves' ballots
    * and first rows [(N + 255) / 256 * 4]; k_autoreset_to's grid (the waves resident at once) */
   float* rt_tab; int rt_rows, rt_n_o; int* rt_cursor; int* rt_env_row; unsigned long long* rt_wave_bal; int* rt_wave_row; int rt_grid;
@@ -117,7 +118,7 @@ static void destroy_handle(rp_sim* h) {        /* frees whatever a (possibly par
   if (!h) return;
   hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dyn); hipFree(h->wrench); hipFree(h->act); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
   hipFree(h->rc_tab); hipFree(h->rc_cnt); hipFree(h->rc_ee);
-  hipFree(h->ep_steps); hipFree(h->ar_list); hipFree(h->ar_ctl); hipFree(h->ar_pair);
+  hipFree(h->ep_steps); hipFree(h->ar_list); hipFree(h->ar_ctl); hipFree(h->ar_pair); hipFree(h->cp_stage);
   hipFree(h->rt_tab); hipFree(h->rt_cursor); hipFree(h->rt_env_row); hipFree(h->rt_wave_bal); hipFree(h->rt_wave_row);
   hipFree(h->rs_state); hipFree(h->rs_idx); hipFree(h->rs_meta); hipFree(h->rs_count); hipFree(h->rs_sort_cnt); hipFree(h->rs_sort_slot); hipFree(h->rs_pair);
   if (h->rs_count_host) hipHostFree(h->rs_count_host);
@@ -809,6 +810,52 @@ int rp_get_actuation(rp_handle h, float* gravity, float* motor_gain, float* moto
   const int N = h->cfg.num_envs, na = h->host_model.n_arm;
   const size_t total = (size_t)N * (3 + 2 * na);
   hipLaunchKernelGGL(k_get_actuation, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->act, gravity, motor_gain, motor_strength, N, na);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+/* enqueued on `stream` like rp_set_wrench; writes the named words of the state records (and, with RP_KIN_CLEAR_CONTACTS, zeroes the cache rows) and nothing else */
+int rp_set_kinematics(rp_handle h, const float* pos, const float* vel, int32_t rows, const uint8_t* mask, uint32_t flags, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  const int N = h->cfg.num_envs, na = h->host_model.n_arm, nf = h->host_model.n_free, nj = h->host_model.n_j1;
+  if (!pos && !vel) { snprintf(h->err, 256, "rp_set_kinematics: pos and vel are both NULL"); return RP_ERR_ARG; }
+  if (rows != 1 && rows != N) { snprintf(h->err, 256, "rp_set_kinematics: rows = %d, expected 1 or num_envs = %d", rows, N); return RP_ERR_ARG; }
+  if (flags & ~(uint32_t)RP_KIN_CLEAR_CONTACTS) { snprintf(h->err, 256, "rp_set_kinematics: unknown bits in flags (0x%x)", flags); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const int nclr = (flags & RP_KIN_CLEAR_CONTACTS) && h->pmcache ? PMC_FLOATS : 0;
+  const size_t total = (size_t)N * (2 * na + 13 * nf + 2 * nj + nclr);
+  hipLaunchKernelGGL(k_set_kinematics, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->state, h->pmcache, pos, vel, (int)rows, mask, N, na, nf,
+                     nj, nclr);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+int rp_get_kinematics(rp_handle h, float* pos, float* vel, void* stream) {
+  if (!h || (!pos && !vel)) { if (h) snprintf(h->err, 256, "rp_get_kinematics: pos and vel are both NULL"); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const int N = h->cfg.num_envs, na = h->host_model.n_arm, nf = h->host_model.n_free, nj = h->host_model.n_j1;
+  const size_t total = (size_t)N * (2 * na + 13 * nf + 2 * nj);
+  hipLaunchKernelGGL(k_get_kinematics, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->state, pos, vel, N, na, nf, nj);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+/* two launches on `stream`: every row into the handle's staging buffer, then the masked envs' rows out of it (k_copy_envs_stage / k_copy_envs_gather) */
+int rp_copy_envs(rp_handle h, const int32_t* src, const uint8_t* mask, uint32_t flags, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  if (!src) { snprintf(h->err, 256, "rp_copy_envs: src is NULL"); return RP_ERR_ARG; }
+  if (flags & ~(uint32_t)RP_COPY_EPISODE_STEPS) { snprintf(h->err, 256, "rp_copy_envs: unknown bits in flags (0x%x)", flags); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const int N = h->cfg.num_envs, nc4 = h->pmcache ? PMC_FLOATS / 4 : 0;
+  const size_t W = RP_REC_FLOATS / 4 + (size_t)nc4, total = (size_t)N * W;
+  if (!h->cp_stage) HIPCHK(h, hipMalloc((void**)&h->cp_stage, total * sizeof(float4) + (size_t)N * sizeof(int)));
+  float4* stage = (float4*)h->cp_stage;
+  int* steps_stage = (int*)(stage + total);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_copy_envs_stage, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, stage, steps_stage, (const float4*)h->state, (const float4*)h->pmcache,
+                     (const int*)h->ep_steps, N, nc4);
+  hipLaunchKernelGGL(k_copy_envs_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (float4*)h->state, (float4*)h->pmcache, h->ep_steps, (const float4*)stage,
+                     (const int*)steps_stage, (const int*)src, mask, N, nc4, (flags & RP_COPY_EPISODE_STEPS) ? 1 : 0);
   HIPCHK(h, hipGetLastError());
   return RP_OK;
 }

@@ -98,6 +98,38 @@ def check_wrench_values(v):
     return t
 
 
+def kinematics_names(model):
+    """{'pos': column names of rp_get_kinematics' pos, 'vel': of its vel} of a baked model.  Both start with the arm's dofs as wrench_names names their links
+    ('link7', in dof order) and end with the scene joints ('door', 'button', 'dial'); between them every free body of wrench_names has seven pos columns
+    ('block.x', '.y', '.z', '.qx', '.qy', '.qz', '.qw') and six vel columns ('block.vx', '.vy', '.vz', '.wx', '.wy', '.wz': world coordinates)"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets', 'models.json')) as f:
+        mdl = next(m for m in json.load(f)['models'] if m['kind'] == model)
+    names = wrench_names(model)
+    na, nf = mdl['n_arm'], len(mdl['free'])
+    arm, free, j1 = list(names[:na]), names[na:na + nf], list(names[na + nf:])
+    pos = arm + ['%s.%s' % (b, c) for b in free for c in ('x', 'y', 'z', 'qx', 'qy', 'qz', 'qw')] + j1
+    vel = arm + ['%s.%s' % (b, c) for b in free for c in ('vx', 'vy', 'vz', 'wx', 'wy', 'wz')] + j1
+    assert len(set(pos)) == len(pos) and len(set(vel)) == len(vel), (pos, vel)
+    return {'pos': tuple(pos), 'vel': tuple(vel)}
+
+
+def check_kinematics_values(what, v, names):
+    """a host-side pos / vel value (sequence, numpy array, CPU tensor; the last axis runs over `names`, a run of kinematics_names columns) as a float32 CPU
+    tensor; every value finite and every quaternion (the four columns from a '.qx' name on) within 1e-3 of unit norm - the library writes the words
+    verbatim (ValueError otherwise)"""
+    t = torch.as_tensor(v, dtype=torch.float32, device='cpu')
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError('%s: values must be finite' % what)
+    if t.dim() == 0 or t.shape[-1] != len(names):
+        raise ValueError('%s: the last axis has %s entries, expected %d' % (what, t.shape[-1] if t.dim() else 'no', len(names)))
+    for k, nm in enumerate(names):
+        if nm.endswith('.qx'):
+            nrm = t[..., k:k + 4].double().norm(dim=-1)
+            if not bool(((nrm - 1.0).abs() <= 1e-3).all()):
+                raise ValueError('%s: the quaternion %s .. qw must have norm 1 within 1e-3' % (what, nm))
+    return t
+
+
 def actuation_names(model):
     """{'gravity': ['x', 'y', 'z'], 'motor': the arm's dofs as wrench_names calls their links ('link7', in dof order)} of a baked model: the columns of
     rp_get_actuation's gravity and of its motor_gain / motor_strength"""
@@ -554,6 +586,124 @@ class VecPlayEnv:
                                                                C.c_void_p(mask.data_ptr()) if mask is not None else None, self._stream()),
                    'rp_set_actuation')
         self._act_src = (parts, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
+
+    @property
+    def kinematics_names(self):
+        """{'pos': a name per column of get_kinematics()['pos'], 'vel': of ['vel']}: arm dofs, free bodies' pose / velocity components, scene joints"""
+        names = getattr(self, '_kin_names', None)
+        if names is None:          # (read from the bake once per handle: set_body / set_joint look columns up in every call)
+            names = self._kin_names = kinematics_names(MODEL_OF[self.env_id])
+        return dict(names)
+
+    def get_kinematics(self):
+        """{'pos': [N, n_pos], 'vel': [N, n_vel]} float32 device tensors: every env's joint positions, free-body poses (x y z qx qy qz qw) and scene-joint
+        positions, and the matching velocities (free bodies: world linear and angular), columns as kinematics_names has them"""
+        names = self.kinematics_names
+        p = torch.empty((self.num_envs, len(names['pos'])), dtype=torch.float32, device=self.device)
+        v = torch.empty((self.num_envs, len(names['vel'])), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib, self.h, self.lib.rp_get_kinematics(self.h, C.c_void_p(p.data_ptr()), C.c_void_p(v.data_ptr()), self._stream()), 'rp_get_kinematics')
+        return {'pos': p, 'vel': v}
+
+    def set_kinematics(self, pos=None, vel=None, mask=None, clear_contacts=False):
+        """Write joint positions / body poses ([N, n_pos] or [n_pos]: every env the same) and / or velocities ([N, n_vel] or [n_vel]) into the state of the envs
+        where mask [N] != 0 (None: all); None leaves that half as it is.  The words are written verbatim and nothing else changes (motor targets, goal,
+        quaternion memory, RNG and episode counters, parameter tables); the contact cache stays unless clear_contacts, which gives the masked envs a state
+        without contact history.  Host values (sequences, numpy, CPU tensors) are checked (finite, unit quaternions within 1e-3); tensors on the env's device
+        are passed through without a host read, so the call can sit in a device-side loop (e.g. mask=done)."""
+        if pos is None and vel is None:
+            raise ValueError('set_kinematics: give pos, vel or both')
+        N, names = self.num_envs, self.kinematics_names
+
+        def prep(what, v):
+            if v is None:
+                return None, 0
+            k = len(names[what])
+            on_dev = isinstance(v, torch.Tensor) and v.device == self.device
+            t = v.to(dtype=torch.float32) if on_dev else check_kinematics_values(what, v, names[what]).to(self.device)
+            if t.dim() == 1 and t.shape[0] == k:
+                return t.contiguous(), 1
+            if t.dim() == 2 and t.shape == (N, k):
+                return t.contiguous(), N
+            raise ValueError('set_kinematics: %s has shape %s, expected [%d] or [%d, %d]' % (what, tuple(t.shape), k, N, k))
+
+        parts = [prep('pos', pos), prep('vel', vel)]
+        rows = max(r for _, r in parts)      # one call, one row count: a single row is broadcast when the other half has N
+        parts = [t.expand(N, -1).contiguous() if t is not None and r != rows else t for t, r in parts]
+        mask = self._mask('set_kinematics', mask)
+        _lib.check(self.lib, self.h, self.lib.rp_set_kinematics(self.h, *[C.c_void_p(t.data_ptr()) if t is not None else None for t in parts], rows,
+                                                                C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                                                                _lib.KIN_CLEAR_CONTACTS if clear_contacts else 0, self._stream()), 'rp_set_kinematics')
+        self._kin_src = (parts, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
+
+    def _columns(self, what, t, names, cols, v):
+        """t[:, cols] = v ([len(cols)] or [N, len(cols)]; a device tensor as it is, host values checked as columns `names`)"""
+        on_dev = isinstance(v, torch.Tensor) and v.device == self.device
+        x = v.to(dtype=torch.float32) if on_dev else check_kinematics_values(what, v, names).to(self.device)
+        if tuple(x.shape) not in ((len(names),), (self.num_envs, len(names))):
+            raise ValueError('%s has shape %s, expected [%d] or [%d, %d]' % (what, tuple(x.shape), len(names), self.num_envs, len(names)))
+        t[:, cols[0]:cols[0] + len(cols)] = x
+
+    def set_body(self, name, pos=None, quat=None, lin_vel=None, ang_vel=None, mask=None, clear_contacts=False):
+        """Place one free body of wrench_names ('block', 'drawer', ...): position (3 values or [N, 3]), orientation quaternion (xyzw, 4 or [N, 4]), world linear
+        and angular velocity (3 or [N, 3]) for the envs where mask != 0 (None: all); None leaves that part as it is.  A read of the tables, a column
+        assignment on the device and set_kinematics; an unknown name raises KeyError."""
+        if pos is None and quat is None and lin_vel is None and ang_vel is None:
+            raise ValueError('set_body: give pos, quat, lin_vel, ang_vel or several')
+        names = self.kinematics_names
+        if name + '.x' not in names['pos']:
+            raise KeyError('set_body: %r is not a free body of %s' % (name, self.env_id))
+        p0, v0 = names['pos'].index(name + '.x'), names['vel'].index(name + '.vx')
+        kin = self.get_kinematics()
+        for what, tab, v, c0, k in (('pos', 'pos', pos, p0, 3), ('quat', 'pos', quat, p0 + 3, 4), ('lin_vel', 'vel', lin_vel, v0, 3), ('ang_vel', 'vel', ang_vel, v0 + 3, 3)):
+            if v is not None:
+                self._columns('set_body: ' + what, kin[tab], names[tab][c0:c0 + k], range(c0, c0 + k), v)
+        self.set_kinematics(pos=kin['pos'] if pos is not None or quat is not None else None,
+                            vel=kin['vel'] if lin_vel is not None or ang_vel is not None else None, mask=mask, clear_contacts=clear_contacts)
+
+    def set_joint(self, name, q=None, qd=None, mask=None):
+        """Set the position and / or velocity (a number or [N]) of one arm dof ('link7') or scene joint ('door', 'button', 'dial') for the envs where mask != 0
+        (None: all); None leaves that half as it is.  The arm's motors keep their targets: a position-controlled dof is driven back unless the next action
+        asks for the new position.  An unknown name raises KeyError."""
+        if q is None and qd is None:
+            raise ValueError('set_joint: give q, qd or both')
+        names = self.kinematics_names
+        if name not in names['pos'] or '.' in name:
+            raise KeyError('set_joint: %r is neither a dof nor a scene joint of %s' % (name, self.env_id))
+        kin = self.get_kinematics()
+        for what, tab, v in (('q', 'pos', q), ('qd', 'vel', qd)):
+            if v is not None:
+                on_dev = isinstance(v, torch.Tensor) and v.device == self.device
+                x = v if on_dev else torch.as_tensor(v, dtype=torch.float32, device='cpu')
+                if tuple(x.shape) not in ((), (self.num_envs,)):
+                    raise ValueError('set_joint: %s has shape %s, expected a number or [%d]' % (what, tuple(x.shape), self.num_envs))
+                c = names[tab].index(name)
+                self._columns('set_joint: ' + what, kin[tab], (name,), (c,), x[..., None])
+        self.set_kinematics(pos=kin['pos'] if q is not None else None, vel=kin['vel'] if qd is not None else None, mask=mask)
+
+    def clone_envs(self, src, mask=None, episode_steps=True):
+        """Every env e where mask [N] != 0 (None: all) becomes a copy of env src[e] as it was before the call (src: int tensor or sequence [N]): state record
+        and contact cache, and with episode_steps its episode counter - on the device, for any src (permutations, many-to-one: resampling, broadcasting one
+        env to a population).  The parameter tables (dynamics, wrench, actuation) and the reset table are not copied.  A host src is range-checked
+        (ValueError); a tensor on the env's device is passed through without a host read, and an entry outside [0, N) leaves its env unchanged."""
+        N = self.num_envs
+        if isinstance(src, torch.Tensor) and src.device == self.device:
+            if src.dtype.is_floating_point or src.dtype == torch.bool:
+                raise ValueError('clone_envs: src must be an integer tensor')
+            t = src.to(dtype=torch.int32)
+        else:
+            t = torch.as_tensor(src, device='cpu')
+            if t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise ValueError('clone_envs: src must hold integers')
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) >= N):
+                raise ValueError('clone_envs: src must lie in [0, %d)' % N)
+            t = t.to(dtype=torch.int32).to(self.device)
+        if t.shape != (N,):
+            raise ValueError('clone_envs: src has shape %s, expected [%d]' % (tuple(t.shape), N))
+        t = t.contiguous()
+        mask = self._mask('clone_envs', mask)
+        _lib.check(self.lib, self.h, self.lib.rp_copy_envs(self.h, C.c_void_p(t.data_ptr()), C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                                                           _lib.COPY_EPISODE_STEPS if episode_steps else 0, self._stream()), 'rp_copy_envs')
+        self._clone_src = (t, mask)      # (kept until the next call: the kernel reads them when the stream gets there)
 
     def calc_state(self):
         self._flip_pack()

@@ -1,0 +1,140 @@
+"""Per-env joint and body state by column and env cloning (rp_get_kinematics / rp_set_kinematics / rp_copy_envs) on a GPU-less host: declared in
+include/rp_playroom.h, exported by both libraries together with their kernels, mirrored in _lib and VecPlayEnv; the column names against the bake and
+against wrench_names; the host-side value checks."""
+import ctypes
+import inspect
+import json
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ('rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs')
+KERNELS = (b'k_set_kinematics', b'k_get_kinematics', b'k_copy_envs_stage', b'k_copy_envs_gather')
+KINDS = ('U', 'R', 'P', 'Q', 'V', 'W')
+
+
+def _header():
+    src = open(os.path.join(REPO, 'include', 'rp_playroom.h')).read()
+    return re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+
+
+def _decl(src, name):
+    return ' '.join(re.search(r'int %s\((.*?)\);' % name, src, flags=re.S).group(1).replace(',', ' , ').split())
+
+
+def test_entry_points_are_declared():
+    src = _header()
+    assert _decl(src, 'rp_get_kinematics') == 'rp_handle h , float* pos , float* vel , void* stream'
+    assert _decl(src, 'rp_set_kinematics') == ('rp_handle h , const float* pos , const float* vel , int32_t rows , const uint8_t* mask , uint32_t flags , '
+                                               'void* stream')
+    assert _decl(src, 'rp_copy_envs') == 'rp_handle h , const int32_t* src , const uint8_t* mask , uint32_t flags , void* stream'
+    assert re.search(r'enum rp_kin_flags \{ RP_KIN_CLEAR_CONTACTS = 1 \};', src)
+    assert re.search(r'enum rp_copy_flags \{ RP_COPY_EPISODE_STEPS = 1 \};', src)
+
+
+def test_entry_points_are_exported_by_both_libraries_and_mirrored():
+    from roboticsplayroompybullet_amd import _lib
+    _lib.build()
+    for path in (_lib.LIB_PATH, _lib.WIDE_LIB_PATH):
+        out = subprocess.run(['nm', '-D', '--defined-only', path], check=True, capture_output=True, text=True).stdout
+        exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == 'T'}
+        for name in NEW:
+            assert name in exported, (name, path)
+        blob = open(path, 'rb').read()
+        for k in KERNELS:
+            assert k in blob, (k, path)
+    for name in NEW:
+        assert name in _lib.EXPORTS, name
+    assert (_lib.KIN_CLEAR_CONTACTS, _lib.COPY_EPISODE_STEPS) == (1, 1)
+    vp = ctypes.c_void_p
+    n_args = {name: len(_decl(_header(), name).split(' , ')) for name in NEW}
+    for wide in (False, True):
+        lib = _lib.load(wide=wide)
+        assert lib.rp_get_kinematics.argtypes == [vp, vp, vp, vp]
+        assert lib.rp_set_kinematics.argtypes == [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_uint32, vp]
+        assert lib.rp_copy_envs.argtypes == [vp, vp, vp, ctypes.c_uint32, vp]
+        for name in NEW:          # the binding's arity is the declaration's
+            assert len(getattr(lib, name).argtypes) == n_args[name], name
+
+
+def test_vec_env_has_the_kinematics_methods():
+    from roboticsplayroompybullet_amd import VecPlayEnv
+    assert isinstance(inspect.getattr_static(VecPlayEnv, 'kinematics_names'), property)
+    assert list(inspect.signature(VecPlayEnv.get_kinematics).parameters) == ['self']
+    p = inspect.signature(VecPlayEnv.set_kinematics).parameters
+    assert list(p) == ['self', 'pos', 'vel', 'mask', 'clear_contacts']
+    assert all(p[k].default is None for k in ('pos', 'vel', 'mask')) and p['clear_contacts'].default is False
+    p = inspect.signature(VecPlayEnv.set_body).parameters
+    assert list(p) == ['self', 'name', 'pos', 'quat', 'lin_vel', 'ang_vel', 'mask', 'clear_contacts']
+    assert all(p[k].default is None for k in ('pos', 'quat', 'lin_vel', 'ang_vel', 'mask')) and p['clear_contacts'].default is False
+    p = inspect.signature(VecPlayEnv.set_joint).parameters
+    assert list(p) == ['self', 'name', 'q', 'qd', 'mask']
+    assert all(p[k].default is None for k in ('q', 'qd', 'mask'))
+    p = inspect.signature(VecPlayEnv.clone_envs).parameters
+    assert list(p) == ['self', 'src', 'mask', 'episode_steps']
+    assert p['mask'].default is None and p['episode_steps'].default is True
+
+
+@pytest.mark.parametrize('kind', KINDS)
+def test_kinematics_names_follow_the_bake(kind):
+    """n_pos = n_arm + 7 n_free + n_j1 and n_vel = n_arm + 6 n_free + n_j1 names, unique; both start with wrench_names' arm links and end with its scene
+    joints, and every free body of wrench_names has its seven / six components in between, in wrench_names' order"""
+    from roboticsplayroompybullet_amd.vec_env import kinematics_names, wrench_names
+    mdl = next(m for m in json.load(open(os.path.join(REPO, 'roboticsplayroompybullet_amd', 'assets', 'models.json')))['models'] if m['kind'] == kind)
+    na, nf, nj = mdl['n_arm'], len(mdl['free']), len(mdl['joint1'])
+    names, wn = kinematics_names(kind), wrench_names(kind)
+    assert set(names) == {'pos', 'vel'}
+    pos, vel = names['pos'], names['vel']
+    assert isinstance(pos, tuple) and isinstance(vel, tuple)
+    assert len(pos) == na + 7 * nf + nj and len(set(pos)) == len(pos)
+    assert len(vel) == na + 6 * nf + nj and len(set(vel)) == len(vel)
+    assert pos[:na] == wn[:na] and vel[:na] == wn[:na]
+    assert all(n.startswith('link') for n in pos[:na])
+    for f, body in enumerate(wn[na:na + nf]):
+        assert pos[na + 7 * f:na + 7 * f + 7] == tuple('%s.%s' % (body, c) for c in ('x', 'y', 'z', 'qx', 'qy', 'qz', 'qw'))
+        assert vel[na + 6 * f:na + 6 * f + 6] == tuple('%s.%s' % (body, c) for c in ('vx', 'vy', 'vz', 'wx', 'wy', 'wz'))
+    assert pos[na + 7 * nf:] == wn[na + nf:] and vel[na + 6 * nf:] == wn[na + nf:]
+    if kind == 'U':
+        assert (na, nf, nj) == (12, 2, 3) and 'block.qw' in pos and 'drawer.y' in pos and pos[-3:] == ('door', 'button', 'dial')
+
+
+def test_host_values_are_checked():
+    import torch
+    from roboticsplayroompybullet_amd.vec_env import check_kinematics_values, kinematics_names
+    names = kinematics_names('U')
+    np_, nv = len(names['pos']), len(names['vel'])
+    good = np.zeros(np_)
+    for k, nm in enumerate(names['pos']):
+        if nm.endswith('.qw'):
+            good[k] = 1.0
+    t = check_kinematics_values('pos', good, names['pos'])
+    assert t.dtype == torch.float32 and t.tolist() == good.tolist()
+    assert check_kinematics_values('pos', np.tile(good, (4, 1)), names['pos']).shape == (4, np_)
+    assert check_kinematics_values('vel', [0.5] * nv, names['vel']).tolist() == [0.5] * nv
+    s = math.sqrt(0.5)
+    assert check_kinematics_values('quat', [s, 0.0, -s, 0.0], names['pos'][15:19]).shape == (4,)
+    assert check_kinematics_values('quat', [0.0, 0.0, 0.0, 1.0005], names['pos'][15:19]).shape == (4,)          # inside the 1e-3 band
+    q = names['pos'].index('drawer.qx')
+    for k, v in ((0, math.nan), (3, math.inf), (np_ - 1, -math.inf)):
+        bad = good.copy(); bad[k] = v
+        with pytest.raises(ValueError):
+            check_kinematics_values('pos', bad, names['pos'])
+    bad = good.copy(); bad[q + 3] = 1.01          # a quaternion of norm 1.01
+    with pytest.raises(ValueError):
+        check_kinematics_values('pos', bad, names['pos'])
+    bad = good.copy(); bad[q + 3] = 0.0           # ... and of norm 0
+    with pytest.raises(ValueError):
+        check_kinematics_values('pos', torch.tensor(bad), names['pos'])
+    with pytest.raises(ValueError):
+        check_kinematics_values('quat', [0.0, 0.0, 0.0, 0.99], names['pos'][15:19])
+    with pytest.raises(ValueError):
+        check_kinematics_values('vel', [math.nan] * nv, names['vel'])
+    with pytest.raises(ValueError):
+        check_kinematics_values('vel', np.array([[math.inf] * nv]), names['vel'])
+    with pytest.raises(ValueError):
+        check_kinematics_values('pos', good[:-1], names['pos'])          # a wrong width
