@@ -153,7 +153,7 @@ struct __align__(16) PrepLds {
   float st[RP_REC_FLOATS];
   int roff[64];
   int slot[64];
-  unsigned amask[4];
+  unsigned amask[4];                           /* lower-limit mask | upper-limit mask | number of small rows (wave 1) | number of torsional rows (wave 0, behind the join: for wave 1) */
   int hdr[4];                                  /* ncon (wave 0) | gear present (wave 1) */
   float O[4];
   float S[RP_MAX_ARM * 6];
@@ -199,6 +199,8 @@ static_assert(offsetof(EnvLds, aabb) % 16 == 0 && offsetof(PrepLds, aabb) % 16 =
 static_assert(sizeof(PrepLds) <= 20480 - 512, "k_prep2: eight blocks (sixteen waves: what its 128 VGPRs allow) per CU");
 static_assert(offsetof(PrepLds, roff) % 16 == 0 && offsetof(PrepLds, slot) % 16 == 0 && offsetof(PrepLds, Minv) % 16 == 0 && offsetof(PrepLds, aout) % 16 == 0 &&
               offsetof(PrepLds, Md) % 8 == 0 && offsetof(PrepLds, cand) % 16 == 0 && offsetof(PrepLds, man) % 16 == 0, "16-byte copies out of LDS");
+static_assert(offsetof(PrepLds, rowS) % 16 == 0 && offsetof(PrepLds, rowT) % 16 == 0 && offsetof(PrepLds, J) % 8 == 0 && offsetof(PrepLds, B) % 8 == 0 && ROWW % 2 == 0,
+              "prep2_core copies rowS / rowT a row (16 bytes) and J / B a pair (8 bytes) at a time");
 
 /* ObsLds: k_calc_state alone - the record, the body transforms (and fk_bodies' scratch), the joint subspaces, the output block: 2.8 KB instead of EnvLds' 17, so that
  * every env of a 4096-env step is resident at once (EnvLds: six blocks per CU, three rounds - 0.048 ms for a kernel that assembles an observation) */
@@ -399,19 +401,8 @@ __device__ __forceinline__ void fk_bodies(const DevModel* m, LDS& L, int lane) {
     par = m->arm_parent[lane];
     if (par < 0) { M3 Rb = ldm3(m->base_rot); V3 pb = ld3(m->base_pos); x.p = pb + mulv(Rb, x.p); x.R = mul(Rb, x.R); }
   }
-  for (int it = 0; __ballot(par >= 0) != 0ull; it++) {      /* wave-uniform trip count */
-    float* Tb = T + (it & 1) * 12 * RP_MAX_ARM;
-    int* Pb = P + (it & 1) * RP_MAX_ARM;
-    if (lane < n) { stm3(&Tb[12 * lane], x.R); st3(&Tb[12 * lane + 9], x.p); Pb[lane] = par; }
-    WSYNC();
-    if (par >= 0) {
-      M3 Ra = ldm3(&Tb[12 * par]); V3 pa = ld3(&Tb[12 * par + 9]);
-      x.p = pa + mulv(Ra, x.p); x.R = mul(Ra, x.R);
-      par = Pb[par];
-    }
-  }
-  /* link j (lane j) is body j + 1; the other bodies (world, free bodies, scene joints) are stored by the lane of their index */
-  if (lane < n) { stm3(&L.xR[9 * (lane + 1)], x.R); st3(&L.xp[3 * (lane + 1)], x.p); }
+  /* link j (lane j) is body j + 1; the other bodies (world, free bodies, scene joints) are stored by the lane of their index - ahead of the arm's loop, which
+   * needs nothing of theirs (their model loads, sincos and stores need not stand behind it; measured: no difference either way) */
   if (lane < m->nbody && !(lane >= 1 && lane <= n)) {
     int b = lane;
     Xf y; y.R = ident3(); y.p = mk3(0, 0, 0);
@@ -431,6 +422,18 @@ __device__ __forceinline__ void fk_bodies(const DevModel* m, LDS& L, int lane) {
     }
     stm3(&L.xR[9 * b], y.R); st3(&L.xp[3 * b], y.p);
   }
+  for (int it = 0; __ballot(par >= 0) != 0ull; it++) {      /* wave-uniform trip count */
+    float* Tb = T + (it & 1) * 12 * RP_MAX_ARM;
+    int* Pb = P + (it & 1) * RP_MAX_ARM;
+    if (lane < n) { stm3(&Tb[12 * lane], x.R); st3(&Tb[12 * lane + 9], x.p); Pb[lane] = par; }
+    WSYNC();
+    if (par >= 0) {
+      M3 Ra = ldm3(&Tb[12 * par]); V3 pa = ld3(&Tb[12 * par + 9]);
+      x.p = pa + mulv(Ra, x.p); x.R = mul(Ra, x.R);
+      par = Pb[par];
+    }
+  }
+  if (lane < n) { stm3(&L.xR[9 * (lane + 1)], x.R); st3(&L.xp[3 * (lane + 1)], x.p); }
 }
 
 /* joint motion subspaces about the reference point O (the EE body's origin), world axes */
@@ -1590,6 +1593,31 @@ __device__ __forceinline__ int manifold_replace_index(const float* c4, const flo
   return best;
 }
 
+/* Contacts leave in solver order (stable partition of the manifold order, the oracle's collide() explains it): key 2 * (touches both
+ * halves of the velocity layout) + (arm link against a movable body).  A lane's points all belong to one object pair, hence to one
+ * key; exclusive prefixes of the per-lane counts (0..4) per key come from ballots.  kept, pk: the lane's manifold (its number of points that
+ * reach the list, its pair key with the classes narrowphase_coop wrote into it); returns the manifold's class and the place of its first
+ * point, and the length of the list */
+__device__ __forceinline__ int solver_place(const int kept, const int pk, const unsigned long long lower, int& cls, int& before) {
+  int key = 0, total = 0;
+  cls = 0; before = 0;          /* points of smaller keys + points of my key in earlier lanes */
+  if (kept > 0) { cls = (pk >> 20) & 3; key = 2 * (cls == 2 ? 1 : 0) + ((pk >> 22) & 1); }
+  unsigned long long mk[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) mk[k] = __ballot(kept > 0 && key == k);
+#pragma unroll
+  for (int bit = 0; bit < 3; bit++) {
+    const unsigned long long mb = __ballot((kept >> bit) & 1);
+    total += __popcll(mb) << bit;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int all = __popcll(mb & mk[k]) << bit, low = __popcll(mb & mk[k] & lower) << bit;
+      before += k < key ? all : (k == key ? low : 0);
+    }
+  }
+  return total;
+}
+
 /* broadphase + narrowphase + manifolds -> L.con*, returns ncon (wave-uniform) */
 template <class LDS>
 __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int env, const int* npm_early = nullptr) {
@@ -1640,7 +1668,7 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
    * first lane of a run merges it (sequentially, in candidate order) into L.man at that place - and only if the list still has room
    * for at least one of its points (cap MAXC, in manifold order). */
   const unsigned long long lower = (1ull << lane) - 1ull;
-  int kept = 0, pk = 0;
+  int kept = 0, pk = 0, total = 0;
   float* man = L.man;
   if (m->persist) {
     /* 3'. PERSISTENT manifolds (oracle collide_persistent): the env's contact cache - one manifold per object pair in creation order, <= 4 points kept in the
@@ -1662,42 +1690,61 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
     WSYNC();
     PCLK(21)
     int npm = uni(__float_as_int(C[0]));
-    {                                                        /* (a) */
-      const int mykey = lane < npm ? __float_as_int(C[PMC_HDR + PMC_MAN * lane]) : -1;
-      const int akey = L.key[lane < nact ? lane : 0];      /* pair k's key waits in lane k: the loops below read lanes, not LDS (a dependent LDS round trip per iteration until round 5) */
+    /* The steady state - no manifold leaves, none is created: nearly every env-substep (lock-step) - is known from the keys the lanes hold once
+     * (a)'s search is done: every manifold touched, and every object pair's first active pair finds its key among them.  Then (a) has nothing to close, (b) nothing
+     * to create, manifold j's key stays in lane j for (c), and neither their passes over LDS nor their syncs run */
+    const int mykey = lane < npm ? __float_as_int(C[PMC_HDR + PMC_MAN * lane]) : -1;      /* manifold j's key in lane j, as loaded */
+    const int akey = L.key[lane < nact ? lane : 0];      /* pair k's key waits in lane k: the loops below read lanes, not LDS (a dependent LDS round trip per iteration until round 5) */
+    const int pkey = L.key[lane >= 1 && lane < nact ? lane - 1 : 0];      /* ... and its predecessor's */
+    bool steady;
+    unsigned long long keep;
+    {                                                        /* (a), the search: both paths */
       bool touched = false; int fl = 0;
       for (int k = 0; k < nact; k++) { const int kk = __builtin_amdgcn_readlane(akey, k); if ((kk & 0xFFFF) == mykey) { touched = true; fl = kk >> 16; } }
+      /* (the steady path runs no sync behind this store: a wave's LDS operations stay in order, and nobody reads a header's word 3 before (e), three syncs on) */
       if (touched) C[PMC_HDR + PMC_MAN * lane + 3] = __int_as_float(fl);
-      const unsigned long long keep = __ballot(touched);
-      WSYNC();
-      int nk = 0;
-      for (int j = 0; j < npm; j++)
-        if ((keep >> j) & 1ull) {
-          if (nk != j && lane < PMC_MAN) C[PMC_HDR + PMC_MAN * nk + lane] = C[PMC_HDR + PMC_MAN * j + lane];
-          nk++;
-        }
-      npm = nk;
-      WSYNC();
-    }
-    {                                                        /* (b) the collider pairs of one object pair are neighbours in the pair list */
-      const int objk = lane < nact ? (L.key[lane] & 0xFFFF) : -1;
-      const bool first = lane < nact && (lane == 0 || (L.key[lane - 1] & 0xFFFF) != objk);
-      const int mkey = __float_as_int(C[PMC_HDR + PMC_MAN * (lane < npm ? lane : 0)]);      /* (after the ranks closed) manifold j's key in lane j */
-      bool present = false;
-      for (int j = 0; j < npm; j++) present |= __builtin_amdgcn_readlane(mkey, j) == objk;
-      const bool isnew = first && !present;
-      const unsigned long long mnew = __ballot(isnew);
-      const int slot = npm + __popcll(mnew & lower);
-      if (isnew && slot < PM_MAX) {
-        const int pi = L.act[lane];
-        float* M = &C[PMC_HDR + PMC_MAN * slot];
-        M[0] = __int_as_float(objk); M[1] = __int_as_float(0);
-        M[2] = fminf(m->col_margin[m->pair[pi][0]], m->col_margin[m->pair[pi][1]]);
-        M[3] = __int_as_float(L.key[lane] >> 16);
-        for (int t = 4; t < PMC_MAN; t++) M[t] = 0.f;        /* (the slot was not loaded: what lies there is narrowphase scratch, and the cache is part of the state rows) */
+      keep = __ballot(touched);
+      steady = keep == (1ull << npm) - 1ull;                 /* (npm <= PM_MAX = 11) */
+      if (steady) {                                          /* (b)'s question, on the keys as loaded: they are where (b) would find them */
+        const int objk = lane < nact ? (akey & 0xFFFF) : -1;
+        const bool first = lane < nact && (lane == 0 || (pkey & 0xFFFF) != objk);
+        bool present = false;
+        for (int j = 0; j < npm; j++) present |= __builtin_amdgcn_readlane(mykey, j) == objk;
+        steady = __ballot(first && !present) == 0ull;
       }
-      npm = min(PM_MAX, npm + (int)__popcll(mnew));
-      WSYNC();
+    }
+    if (!steady) {                                           /* THE GENERAL PATH: a manifold leaves or one is created (the steady path: nothing to do) */
+      {                                                      /* (a), the rest: close ranks */
+        WSYNC();
+        int nk = 0;
+        for (int j = 0; j < npm; j++)
+          if ((keep >> j) & 1ull) {
+            if (nk != j && lane < PMC_MAN) C[PMC_HDR + PMC_MAN * nk + lane] = C[PMC_HDR + PMC_MAN * j + lane];
+            nk++;
+          }
+        npm = nk;
+        WSYNC();
+      }
+      {                                                      /* (b) the collider pairs of one object pair are neighbours in the pair list */
+        const int objk = lane < nact ? (L.key[lane] & 0xFFFF) : -1;
+        const bool first = lane < nact && (lane == 0 || (L.key[lane - 1] & 0xFFFF) != objk);
+        const int mkey = __float_as_int(C[PMC_HDR + PMC_MAN * (lane < npm ? lane : 0)]);      /* (after the ranks closed) manifold j's key in lane j */
+        bool present = false;
+        for (int j = 0; j < npm; j++) present |= __builtin_amdgcn_readlane(mkey, j) == objk;
+        const bool isnew = first && !present;
+        const unsigned long long mnew = __ballot(isnew);
+        const int slot = npm + __popcll(mnew & lower);
+        if (isnew && slot < PM_MAX) {
+          const int pi = L.act[lane];
+          float* M = &C[PMC_HDR + PMC_MAN * slot];
+          M[0] = __int_as_float(objk); M[1] = __int_as_float(0);
+          M[2] = fminf(m->col_margin[m->pair[pi][0]], m->col_margin[m->pair[pi][1]]);
+          M[3] = __int_as_float(L.key[lane] >> 16);
+          for (int t = 4; t < PMC_MAN; t++) M[t] = 0.f;        /* (the slot was not loaded: what lies there is narrowphase scratch, and the cache is part of the state rows) */
+        }
+        npm = min(PM_MAX, npm + (int)__popcll(mnew));
+        WSYNC();
+      }
     }
     PCLK(22)
     /* (c) one lane per CANDIDATE (at most CANDMAX = 64): its manifold, its two points in the bodies' frames, the nearest cached point within the threshold
@@ -1713,7 +1760,13 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
       const float dist = c[6];
       const int abw = __float_as_int(c[7]);
       const int objk = L.key[(abw >> 16) & 63] & 0xFFFF;
-      const int mkey = __float_as_int(C[PMC_HDR + PMC_MAN * (lane < npm ? lane : 0)]);      /* manifold j's key in lane j (the new ones included) */
+      /* the candidate's two points in its bodies' frames need the candidate and the FK alone: their gathers of xR / xp are asked for here, beside the key and header
+       * reads of the manifold search, not behind them */
+      const int ba = (abw >> 22) & 31, bb = (abw >> 27) & 31;
+      const M3 RA = ldm3(&L.xR[9 * ba]), RB = ldm3(&L.xR[9 * bb]);
+      const V3 xA = ld3(&L.xp[3 * ba]), xB = ld3(&L.xp[3 * bb]);
+      const int mkey = steady ? mykey : __float_as_int(C[PMC_HDR + PMC_MAN * (lane < npm ? lane : 0)]);      /* manifold j's key in lane j (the new ones included; the steady
+                                                                                                                * state: as loaded, nothing moved) */
       int mi = -1;
       for (int jm = 0; jm < npm; jm++) if (__builtin_amdgcn_readlane(mkey, jm) == objk) mi = jm;
       if (!isc) mi = -1;
@@ -1721,9 +1774,8 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
       const float thr = M[2];
       if (dist > thr) mi = -1;
       const int n = __float_as_int(M[1]);
-      const int ba = (abw >> 22) & 31, bb = (abw >> 27) & 31;
-      const V3 lA = tmulv(ldm3(&L.xR[9 * ba]), p + nr * (0.5f * dist) - ld3(&L.xp[3 * ba]));
-      const V3 lB = tmulv(ldm3(&L.xR[9 * bb]), p - nr * (0.5f * dist) - ld3(&L.xp[3 * bb]));
+      const V3 lA = tmulv(RA, p + nr * (0.5f * dist) - xA);
+      const V3 lB = tmulv(RB, p - nr * (0.5f * dist) - xB);
       int sl = -1; float shortest = thr * thr;
       for (int q = 0; q < 4; q++) {
         const V3 d = ld3(&M[8 + PMC_PT * q]) - lA;
@@ -1845,7 +1897,11 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
       for (int bit = 0; bit < 3; bit++) off += __popcll(__ballot((cnt >> bit) & 1) & lower) << bit;
       off = __shfl(off, lane & ~3);                          /* the manifold's first record */
       const int room = max(0, MAXC - off);
-      if (q == 0 && mine) { kept = min(cnt, room); man = &L.man[8 * (off < MANPTS ? off : 0)]; pk = fl << 16; }
+      if (q == 0 && mine) { kept = min(cnt, room); pk = fl << 16; }
+      /* the manifold's place in the solver's order, known before a point has moved: its first lane's, handed to its other three */
+      int cls, before;
+      total = solver_place(kept, pk, lower, cls, before);
+      cls = __shfl(cls, lane & ~3); before = __shfl(before, lane & ~3);
       WSYNC();                                               /* every lane holds its point: the cache slots may be overwritten */
       if (slot >= 0) {
         float* P = &C[PMC_HDR + PMC_MAN * mi + 8 + PMC_PT * slot];
@@ -1855,10 +1911,13 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
       }
       if (q == 0 && mine) C[PMC_HDR + PMC_MAN * mi + 1] = __int_as_float(nn);
       const int ri = single ? 0 : slot;
-      if (emit && ri < room) {
+      if (emit && ri < room) {                               /* the point's own lane writes its contact and looks up its friction: all points of the env at once */
         const V3 pm = (pA + pB) * 0.5f;
-        float* r = &L.man[8 * (off + ri)];
-        r[0] = pm.x; r[1] = pm.y; r[2] = pm.z; r[3] = nr.x; r[4] = nr.y; r[5] = nr.z; r[6] = dist; r[7] = __int_as_float(ab);
+        const int o = before + ri, ca = ab & 255, cb = (ab >> 8) & 255;      /* (the colliders may differ from point to point inside a manifold) */
+        st3(&L.conp[3 * o], pm); st3(&L.conn[3 * o], nr);
+        L.cond[o] = dist;
+        L.cona[o] = ca; L.conb[o] = cb; L.conk[o] = cls;
+        L.conmu[o] = pair_friction(m, L, ca, cb);            /* (a cached point's pair may not be active now: the product from the table) */
       }
     }
     WSYNC();
@@ -1903,28 +1962,9 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
     }
   }
   WSYNC();
-  }
-  /* Contacts leave in solver order (stable partition of the manifold order, the oracle's collide() explains it): key 2 * (touches both
-   * halves of the velocity layout) + (arm link against a movable body).  A lane's points all belong to one object pair, hence to one
-   * key; exclusive prefixes of the per-lane counts (0..4) per key come from ballots. */
-  int cls = 0, key = 0;
-  if (kept > 0) { cls = (pk >> 20) & 3; key = 2 * (cls == 2 ? 1 : 0) + ((pk >> 22) & 1); }      /* (narrowphase_coop wrote the pair's classes into its key) */
-  int before = 0, total = 0;          /* points of smaller keys + points of my key in earlier lanes */
-  {
-    unsigned long long mk[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) mk[k] = __ballot(kept > 0 && key == k);
-#pragma unroll
-    for (int bit = 0; bit < 3; bit++) {
-      const unsigned long long mb = __ballot((kept >> bit) & 1);
-      total += __popcll(mb) << bit;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int all = __popcll(mb & mk[k]) << bit, low = __popcll(mb & mk[k] & lower) << bit;
-        before += k < key ? all : (k == key ? low : 0);
-      }
-    }
-  }
+  /* the merged manifolds leave from L.man, each by its first lane (solver_place: the order) */
+  int cls, before;
+  total = solver_place(kept, pk, lower, cls, before);
   for (int i = 0; i < kept; i++) {
     const float4 c0 = *(const float4*)&man[8 * i], c1 = *(const float4*)&man[8 * i + 4];
     const int ab = __float_as_int(c1.w);              /* the colliders may differ from point to point inside a manifold */
@@ -1933,7 +1973,8 @@ __device__ __forceinline__ int collide(const DevModel* m, LDS& L, int lane, int 
     L.conn[3 * o] = c0.w; L.conn[3 * o + 1] = c1.x; L.conn[3 * o + 2] = c1.y;
     L.cond[o] = c1.z;
     L.cona[o] = ab & 255; L.conb[o] = (ab >> 8) & 255; L.conk[o] = cls;
-    L.conmu[o] = m->persist ? pair_friction(m, L, ab & 255, (ab >> 8) & 255) : L.pmu[(ab >> 16) & 63];      /* (a cached point's pair may not be active now: same product from the table) */
+    L.conmu[o] = L.pmu[(ab >> 16) & 63];
+  }
   }
   WSYNC();
   PCLK(10)
@@ -3648,7 +3689,8 @@ __device__ __forceinline__ void copy_out(float* __restrict__ dst, const float* s
 #define W3_FLOATS (W3_SROW + 4 + 8 * MAXSMALL)
 #define STAGE_FLOATS (128 + 2 * ROWREG)   /* ROFF | SLOT | J | B: contiguous, staged through LDS by k_solve2 */
 #define AOUT_FLOATS (160 + 8 + 20)
-static_assert(W3_A % 4 == 0 && W3_ROWS % 4 == 0 && W3_ROFF % 4 == 0 && AOUT_FLOATS % 4 == 0, "16-byte copies");
+static_assert(W3_A % 4 == 0 && W3_ROWS % 4 == 0 && W3_ROWT % 4 == 0 && W3_ROFF % 4 == 0 && AOUT_FLOATS % 4 == 0 && W3_FLOATS % 4 == 0, "16-byte copies");
+static_assert(W3_J % 2 == 0 && W3_B % 2 == 0, "8-byte copies of the compact rows");
 
 #define HV_MAXC 14                    /* contacts of an env in heavy_solve's first lane register (more: heavy_solve<true>, a second register).  A register layout, no
                                        * oracle counterpart: the oracle's residual form (solve_rows_residual) takes up to MAX_CONTACTS in one.  tests/test_contact_caps.py
@@ -3741,75 +3783,91 @@ __device__ __forceinline__ void prep2_core(PrepLds& L, const DevModel* __restric
   int tid_j = threadIdx.x;
   asm volatile("" : "+v"(tid_j));      /* (the thread's numbers once more, opaque to the compiler: what the phases above derived from them need not survive those phases) */
   const int wid_j = tid_j >> 6;
-  if (wid_j == 0) {
+  {
     const int lane = tid_j & 63;
     float* w = ws + (size_t)env * W3_FLOATS;
-    /* contact classes (collide() ordered them): rank inside the class -> slot tables for k_solve2 */
+    /* contact classes (collide() ordered them): rank inside the class -> slot tables for k_solve2 (wave 0), a torsional row's parent slot (whichever wave copies it) */
     const int cls = lane < ncon ? L.conk[lane] : 3;
     const unsigned long long mB = __ballot(cls == 0), mA = __ballot(cls == 1), mC = __ballot(cls == 2);
     const unsigned long long lower = (1ull << lane) - 1ull;
-    L.slot[lane] = -1;
-    L.roff[lane] = 0;
-    const int nt = tors_list(m, L, lane, ncon);               /* torsional rows */
-    WSYNC();
-    if (cls == 0) L.slot[__popcll(mB & lower)] = lane;             /* s-th contact of the second half (DPP row 1) */
-    else if (cls == 1) L.slot[21 + __popcll(mA & lower)] = lane;   /* s-th contact of the first half (DPP row 0) */
-    else if (cls == 2) L.slot[42 + __popcll(mC & lower)] = lane;   /* j-th contact that touches both */
-    /* contact rows, PREP_CH contacts at a time: built in LDS, then copied to their places in the workspace (row number: normals first,
+    int nt = 0;
+    if (wid_j == 0) {
+      L.slot[lane] = -1;
+      L.roff[lane] = 0;
+      nt = tors_list(m, L, lane, ncon);                         /* torsional rows */
+      if (lane == 0) L.amask[3] = (unsigned)nt;                 /* (for the other wave, behind the first chunk's barrier) */
+      WSYNC();
+      if (cls == 0) L.slot[__popcll(mB & lower)] = lane;             /* s-th contact of the second half (DPP row 1) */
+      else if (cls == 1) L.slot[21 + __popcll(mA & lower)] = lane;   /* s-th contact of the first half (DPP row 0) */
+      else if (cls == 2) L.slot[42 + __popcll(mC & lower)] = lane;   /* j-th contact that touches both */
+    }
+    /* contact rows, PREP_CH contacts at a time: built in LDS by wave 0, then copied to their places in the workspace by BOTH waves (row number: normals first,
      * then the friction pairs - the order the one-kernel path builds them in - and behind them, compact rows 3 ncon + t, the torsional rows).
      * The torsional rows ride in the last chunk when it has room for them (its lanes are idle anyway), else in a chunk of their own; k_solve2
      * finds a torsional row's parent - the normal impulse that bounds it - through the parent's class and its rank inside it (= its slot),
-     * packed beside the parent's index */
+     * packed beside the parent's index.
+     * A chunk's normals, torsional rows and friction rows are three runs of neighbouring rows here and there, and a row is 72 bytes: the copy moves 8-byte pairs,
+     * thread t of the block the pairs t, t + 128, ..., its (row, pair) kept by addition; rowS goes by wave 0 and rowT by wave 1, a row (16 bytes) per lane.
+     * Wave 1 learns the number of torsional rows behind the first chunk's barrier (a torsional row has a contact: without contacts neither wave enters the loop) */
     bool tors_done = nt == 0;
     for (int c0 = 0; c0 < ncon || !tors_done; c0 += PREP_CH) {
+      if (c0 > 0) __syncthreads();                              /* the chunk before has left LDS */
       const int nc = max(0, min(PREP_CH, ncon - c0));
-      const int ntl = (!tors_done && c0 + PREP_CH >= ncon && 3 * nc + nt <= 3 * PREP_CH) ? nt : 0;      /* (wave-uniform) */
-      contact_rows(m, L, lane, c0, nc, ntl);
-      WSYNC();
+      if (wid_j == 0) contact_rows(m, L, lane, c0, nc, (!tors_done && c0 + PREP_CH >= ncon && 3 * nc + nt <= 3 * PREP_CH) ? nt : 0);
+      __syncthreads();
+      if (wid_j != 0 && c0 == 0) { nt = (int)L.amask[3]; tors_done = nt == 0; }
+      const int ntl = (!tors_done && c0 + PREP_CH >= ncon && 3 * nc + nt <= 3 * PREP_CH) ? nt : 0;      /* (block-uniform) */
       auto global_row = [&](int lr) { return lr < nc ? c0 + lr : (lr < nc + ntl ? 3 * ncon + (lr - nc) : ncon + 2 * c0 + (lr - nc - ntl)); };
-      for (int e = lane; e < (3 * nc + ntl) * ROWW; e += 64) {
-        const int lr = e / ROWW, k = e - lr * ROWW;
-        const int gr = global_row(lr);
-        w[W3_J + gr * ROWW + k] = L.J[e]; w[W3_B + gr * ROWW + k] = L.B[e];
-      }
-      for (int e = lane; e < (3 * nc + ntl) * 4; e += 64) {
-        const int lr = e >> 2, k = e & 3;
-        const int gr = global_row(lr);
-        float v = L.rowS[e];
-        if (k == 3 && lr >= nc && lr < nc + ntl) {
-          const int c = L.torc[lr - nc], kc = L.conk[c];
-          const unsigned long long mk = kc == 1 ? mA : (kc == 2 ? mC : mB);
-          v = __int_as_float(c | (kc << 8) | (__popcll(mk & ((1ull << c) - 1ull)) << 12));
+      const int nrow = 3 * nc + ntl;
+      {
+        static_assert(ROWW % 2 == 0 && PREP_THREADS / (ROWW / 2) == 14 && PREP_THREADS % (ROWW / 2) == 2, "the copy's (row, pair) step");
+        int lr = tid_j / (ROWW / 2), k = tid_j - lr * (ROWW / 2);      /* (once per chunk; the loop adds) */
+        for (; lr < nrow; ) {
+          const int gr = global_row(lr);
+          *(float2*)&w[W3_J + gr * ROWW + 2 * k] = *(const float2*)&L.J[lr * ROWW + 2 * k];
+          *(float2*)&w[W3_B + gr * ROWW + 2 * k] = *(const float2*)&L.B[lr * ROWW + 2 * k];
+          lr += 14; k += 2;
+          if (k >= ROWW / 2) { k -= ROWW / 2; lr++; }
         }
-        w[W3_ROWS + gr * 4 + k] = v; w[W3_ROWT + gr * 4 + k] = L.rowT[e];
       }
-      if (lane < 3 * nc + ntl && !(lane >= nc && lane < nc + ntl)) {
+      if (lane < nrow) {
         const int gr = global_row(lane);
-        L.roff[gr] = __float_as_int(L.rowT[4 * lane + 2]) | (__float_as_int(L.rowT[4 * lane + 3]) << 8);
+        if (wid_j == 0) {
+          float4 v = *(const float4*)&L.rowS[4 * lane];
+          if (lane >= nc && lane < nc + ntl) {
+            const int c = L.torc[lane - nc], kc = L.conk[c];
+            const unsigned long long mk = kc == 1 ? mA : (kc == 2 ? mC : mB);
+            v.w = __int_as_float(c | (kc << 8) | (__popcll(mk & ((1ull << c) - 1ull)) << 12));
+          }
+          *(float4*)&w[W3_ROWS + gr * 4] = v;
+          if (!(lane >= nc && lane < nc + ntl)) L.roff[gr] = __float_as_int(L.rowT[4 * lane + 2]) | (__float_as_int(L.rowT[4 * lane + 3]) << 8);
+        } else {
+          *(float4*)&w[W3_ROWT + gr * 4] = *(const float4*)&L.rowT[4 * lane];
+        }
       }
       if (ntl > 0) tors_done = true;
+    }
+    if (wid_j == 0) {
       WSYNC();
-    }
-    PCLK(4)
-    if (lane == 0) {
-      int nj = m->n_j1 < NBJ ? m->n_j1 : NBJ;
-      w[W3_HDR] = __int_as_float((int)L.amask[0]); w[W3_HDR + 1] = __int_as_float((int)L.amask[1]);
-      w[W3_HDR + 2] = __int_as_float(nj); w[W3_HDR + 3] = __int_as_float(ncon);
-      w[W3_HDR + 4] = __int_as_float(__popcll(mA)); w[W3_HDR + 5] = __int_as_float(__popcll(mB));
-      w[W3_HDR + 6] = __int_as_float(L.hdr[1] | (nt << 8)); w[W3_HDR + 7] = __int_as_float(__popcll(mC));      /* gear present | torsional rows << 8 */
-      if (hv_list != nullptr && (hv_class(ncon, __popcll(mA), __popcll(mB), __popcll(mC)) != 0 || (prep_flags & 1))) hv_list[atomicAdd(hv_cnt, 1)] = env | (ncon << 24);      /* a heavy env: one of k_solve2's worker blocks to itself */
-    }
-    if (lane < 32) w[W3_MU + lane] = lane < ncon ? L.conmu[lane] : 0.f;
-    copy_out(w + W3_ROFF, (const float*)L.roff, 64, lane);
-    copy_out(w + W3_SLOT, (const float*)L.slot, 64, lane);
-  } else {
-    if ((tid_j & 63) == 0) pair_tab[L.hdr[3]] = env | (ncon << 24);     /* + its contact count: k_solve2 sizes its row copy without waiting for the header */
-    if (prep_flags & 1) {      /* (debug flag 1) super_solve's envs: the typed row list too (it walks the rows the way the one-kernel path does) */
-      const int lane = tid_j & 63;
-      float* w = ws + (size_t)env * W3_FLOATS;
-      const int nsm = (int)L.amask[2];
-      if (lane == 0) w[W3_SROW] = __int_as_float(nsm);
-      for (int i = lane; i < 8 * nsm; i += 64) w[W3_SROW + 4 + i] = L.srow[i];
+      PCLK(4)
+      if (lane == 0) {
+        int nj = m->n_j1 < NBJ ? m->n_j1 : NBJ;
+        w[W3_HDR] = __int_as_float((int)L.amask[0]); w[W3_HDR + 1] = __int_as_float((int)L.amask[1]);
+        w[W3_HDR + 2] = __int_as_float(nj); w[W3_HDR + 3] = __int_as_float(ncon);
+        w[W3_HDR + 4] = __int_as_float(__popcll(mA)); w[W3_HDR + 5] = __int_as_float(__popcll(mB));
+        w[W3_HDR + 6] = __int_as_float(L.hdr[1] | (nt << 8)); w[W3_HDR + 7] = __int_as_float(__popcll(mC));      /* gear present | torsional rows << 8 */
+        if (hv_list != nullptr && (hv_class(ncon, __popcll(mA), __popcll(mB), __popcll(mC)) != 0 || (prep_flags & 1))) hv_list[atomicAdd(hv_cnt, 1)] = env | (ncon << 24);      /* a heavy env: one of k_solve2's worker blocks to itself */
+      }
+      copy_out(w + W3_ROFF, (const float*)L.roff, 64, lane);
+      copy_out(w + W3_SLOT, (const float*)L.slot, 64, lane);
+    } else {
+      if (lane == 0) pair_tab[L.hdr[3]] = env | (ncon << 24);     /* + its contact count: k_solve2 sizes its row copy without waiting for the header */
+      if (lane < 32) w[W3_MU + lane] = lane < ncon ? L.conmu[lane] : 0.f;      /* (the contact list is the join's) */
+      if (prep_flags & 1) {      /* (debug flag 1) super_solve's envs: the typed row list too (it walks the rows the way the one-kernel path does) */
+        const int nsm = (int)L.amask[2];
+        if (lane == 0) w[W3_SROW] = __int_as_float(nsm);
+        for (int i = lane; i < 8 * nsm; i += 64) w[W3_SROW + 4 + i] = L.srow[i];
+      }
     }
   }
   PCLK(5) PCLK(7)
