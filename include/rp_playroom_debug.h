@@ -34,6 +34,12 @@ int rp_debug_reset_rounds(rp_handle h);
 /* k_autoreset's launch shape, fixed at rp_create: *grid = its blocks (the blocks resident at once, or RP_AUTORESET_BLOCKS; never more than
  * ceil(num_envs / epb)), *epb = the envs a block settles side by side (RP_AUTORESET_EPB, 1 .. 4) */
 int rp_debug_autoreset_shape(rp_handle h, int32_t* grid, int32_t* epb);
+/* the action stage alone (clip, action type, IK, clamps, motor targets: k_action's body, 64-thread blocks, 16 lanes per env) on the current state, NULL stream, synchronised.
+ * Blocks are cut by the latest step's member table and group bounds as they stand (the next step would re-rank first); before the first step of a pipeline, in identity
+ * order with rp_set_groups' groups.  action_dev [N][dims.action] (unclipped, as rp_step takes it); raw_dev [N][8] floats: the joint solution BEFORE the clamps to the joint
+ * limits and to q +- inc (7, zero-padded), then 1 * capped + 2 * marginal + 4 * place - the conditions behind status bits 8 and 16, and the env's place in the member table
+ * (place / 4 within its group's launch is its block, place % 4 its DPP row).  As in a step the motor targets and the status word are written into the state; nothing else is. */
+int rp_debug_action(rp_handle h, const float* action_dev, float* raw_dev);
 /* PROFILING BUILDS ONLY (tools/build_profiling_libs.sh: -DRP_CLOCKS=1|2, -DRP_PROLOGUE_CLOCKS, -DRP_CHAIN_CLOCKS).  The shipped library exports none of these and
  * tests/test_abi.py does not expect them; such a build also exports, for the tools that load it through RP_PLAYROOM_LIB:
  *     rp_debug_clocks(rp_handle, uint64_t* host_buf, int32_t nwaves)              s_memtime marks per wave of k_solve2 (RP_CLOCKS=1) / per block of k_prep2 (=2)

@@ -90,6 +90,8 @@ def load(f32=False, bullet_ref=False, abx=False):
     lib.rpo_dial_to_0_1_range.argtypes = [C.c_double]
     lib.rpo_dial_to_0_1_range.restype = C.c_double
     lib.rpo_perform_action.argtypes = [vp, dp, dp]
+    lib.rpo_perform_action_raw.argtypes = [vp, dp, dp]
+    lib.rpo_ik_report.argtypes = [ip]
     lib.rpo_action_target.argtypes = [C.c_int, dp, dp, dp, dp, dp]
     lib.rpo_set_ranges.argtypes = [vp, dp, dp, dp, dp, dp]
     lib.rpo_set_action_type.argtypes = [vp, C.c_int]
@@ -333,6 +335,16 @@ class OracleEnv:
         tp = np.zeros(7)
         self.lib.rpo_perform_action(self.h, _d(action)[1], tp.ctypes.data_as(C.POINTER(C.c_double)))
         return tp[:self.n_target].copy()
+
+    def perform_action_raw(self, action):
+        """the joint poses perform_action hands to goto_joint_poses (unclamped; no motor is set) and what the IK reported on the way:
+        (raw [n_target], dict(calls, passes, capped, window)) - capped / window are what the HIP library's status bits 8 / 16 mean"""
+        jp = np.zeros(7)
+        rep = (C.c_int * 4)()
+        self.lib.rpo_ik_report(rep)
+        self.lib.rpo_perform_action_raw(self.h, _d(action)[1], jp.ctypes.data_as(C.POINTER(C.c_double)))
+        self.lib.rpo_ik_report(rep)
+        return jp[:self.n_target].copy(), dict(calls=rep[0], passes=rep[1], capped=bool(rep[2]), window=bool(rep[3]))
 
     def goto_joint_poses(self, poses, gripper=None):
         tp = np.zeros(7)

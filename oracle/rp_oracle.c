@@ -2117,12 +2117,20 @@ static void solve_spd(real* A, real* b, int n) {   /* Gaussian elimination with 
  * until |dpos| < 1e-4 or max_iter.  All movable dofs take part; non-ancestor columns are zero. */
 static _Thread_local long g_ik_iters = 0;      /* loop passes of ik_solve in the calling thread (tools/ik_histogram.py: what bounds k_action) */
 long rpo_ik_iterations(int reset) { long v = g_ik_iters; if (reset) g_ik_iters = 0; return v; }
+/* what the HIP library reports about a step's IK, for the calls of the calling thread since the last rpo_ik_report: the calls, their loop passes, whether the LAST call ended
+ * without its residual test passing (the library's status bit 8), whether any stopping test fell within 0.5 % of IK_RESIDUAL (status bit 16) */
+static _Thread_local int g_ik_calls = 0, g_ik_passes = 0, g_ik_capped = 0, g_ik_window = 0;
+void rpo_ik_report(int* out4) {
+  out4[0] = g_ik_calls; out4[1] = g_ik_passes; out4[2] = g_ik_capped; out4[3] = g_ik_window;
+  g_ik_calls = g_ik_passes = g_ik_capped = g_ik_window = 0;
+}
 static void ik_solve(const rpo_env* e, const real* pos, const real* quat, const real* q_seed, int max_iter, real* q) {
   const rp_model* m = &e->m;
   int n = m->n_arm;
   for (int i = 0; i < n; i++) q[i] = q_seed[i];
+  g_ik_calls++; g_ik_capped = 1;
   for (int it = 0; it < max_iter; it++) {
-    g_ik_iters++;
+    g_ik_iters++; g_ik_passes++;
     xform xb[1 + RP_MAX_ARM];
     ik_arm_fk(e, q, xb);
     real p[3], R[9], qc[4];
@@ -2137,7 +2145,9 @@ static void ik_solve(const rpo_env* e, const real* pos, const real* quat, const 
     m3_to_quat(qc, R);
     real err[6];
     v3sub(err, pos, p);
-    if (it > 0 && R_SQRT(ik_dot(err, err)) < IK_RESIDUAL) break;
+    const real res = R_SQRT(ik_dot(err, err));
+    if (it > 0 && res > (real)0.995 * IK_RESIDUAL && res < (real)1.005 * IK_RESIDUAL) g_ik_window = 1;
+    if (it > 0 && res < IK_RESIDUAL) { g_ik_capped = 0; break; }
     real qinv[4] = {-qc[0], -qc[1], -qc[2], qc[3]}, dq[4];
     ik_quat_mul(dq, quat, qinv);
     /* btQuaternion::getAngle()/getAxis() = 2 acos(w), v / sqrt(1 - w^2), written in the equivalent
@@ -2316,14 +2326,14 @@ void rpo_action_target(int action_type, const double* action, const double* ee_p
   for (int i = 0; i < 3; i++) pos[i] = p[i];
   for (int i = 0; i < 4; i++) quat[i] = q[i];
 }
-static void perform_action(rpo_env* e, const real* a, real* target_poses) {
-  real quat[4], pos[3], jp[RP_MAX_ARM];
+/* the joint poses perform_action hands to goto_joint_poses (before its two clamps), and the gripper command */
+static real action_joint_poses(rpo_env* e, const real* a, real* jp) {
+  real quat[4], pos[3];
   int nd = e->m.arm_type == RP_ARM_PANDA ? 7 : 6;
   int at = e->action_type;
   if (at == RPO_ACT_ABS_JOINTS || at == RPO_ACT_REL_JOINTS) {
     for (int i = 0; i < nd; i++) jp[i] = at == RPO_ACT_REL_JOINTS ? a[i] + e->q[i] : a[i];
-    goto_joint_poses(e, jp, 1, a[nd], target_poses);
-    return;
+    return a[nd];
   }
   real grip = (at == RPO_ACT_ABS_QUAT || at == RPO_ACT_REL_QUAT) ? a[7] : a[6];
   real cp[3] = {0, 0, 0}, cq[4] = {0, 0, 0, 1};
@@ -2341,6 +2351,11 @@ static void perform_action(rpo_env* e, const real* a, real* target_poses) {
   } else {
     calc_angles(e, pos, quat, e->q, jp);
   }
+  return grip;
+}
+static void perform_action(rpo_env* e, const real* a, real* target_poses) {
+  real jp[RP_MAX_ARM];
+  const real grip = action_joint_poses(e, a, jp);
   goto_joint_poses(e, jp, 1, grip, target_poses);
 }
 
@@ -2375,6 +2390,15 @@ void rpo_perform_action(rpo_env* e, const double* action, double* target_poses) 
   perform_action(e, a, tp);
   int nd = e->m.arm_type == RP_ARM_PANDA ? 7 : 6;
   for (int i = 0; i < nd; i++) target_poses[i] = tp[i];
+}
+
+void rpo_perform_action_raw(rpo_env* e, const double* action, double* joint_poses) {
+  real a[8], jp[RP_MAX_ARM];
+  int na = action_dim(e);
+  for (int i = 0; i < na; i++) a[i] = (real)action[i];
+  action_joint_poses(e, a, jp);
+  int nd = e->m.arm_type == RP_ARM_PANDA ? 7 : 6;
+  for (int i = 0; i < nd; i++) joint_poses[i] = jp[i];
 }
 
 /* ------------------------------------------------------------------ harness: observation */

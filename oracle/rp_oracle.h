@@ -74,6 +74,11 @@ double rpo_dial_to_0_1_range(double x);
 
 /* pieces, exposed for unit tests and goldens */
 void rpo_perform_action(rpo_env*, const double* action_clipped, double* target_poses);   /* environments.py:915-1073 */
+/* the joint poses rpo_perform_action hands to goto_joint_poses, before its clamps to the joint limits and to q +- inc (the IK's own solution for the pose types); sets no motor */
+void rpo_perform_action_raw(rpo_env*, const double* action_clipped, double* joint_poses);
+/* the IK calls of the calling thread since the last rpo_ik_report: out4 = calls, loop passes, the last call ended without its residual test passing (the HIP library's status
+ * bit 8), a stopping test (it > 0) fell in 0.995 .. 1.005 x the residual threshold (status bit 16); then clears them */
+void rpo_ik_report(int* out4);
 void rpo_goto_joint_poses(rpo_env*, const double* joint_poses, int has_gripper, double gripper, double* target_poses);
 void rpo_ik(const rpo_env*, const double* pos, const double* quat, const double* q_seed, int max_iter, double* q_out);
 void rpo_calc_angles(const rpo_env*, const double* pos, const double* quat, const double* current, double* q_out); /* inverseKinematics.py:44-50 */

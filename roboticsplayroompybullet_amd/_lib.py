@@ -86,7 +86,7 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
-                 'rp_debug_autoreset_shape']
+                 'rp_debug_autoreset_shape', 'rp_debug_action']
 
 _lib = None
 _libs = {}
@@ -160,6 +160,7 @@ def load(wide=False):
     lib.rp_debug_row_counts.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.rp_debug_reset_rounds.argtypes = [vp]
     lib.rp_debug_autoreset_shape.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.rp_debug_action.argtypes = [vp, vp, vp]
     _libs[path] = lib
     if not wide:
         _lib = lib

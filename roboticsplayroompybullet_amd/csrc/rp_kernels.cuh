@@ -3572,7 +3572,8 @@ __global__ void k_get_actuation(const float* __restrict__ tab, float* __restrict
  *   k_calc_state (wave per env) calc_state + reward + outputs */
 /* perform_action (environments.py:915-1073), 16 lanes (one DPP row) per env, four envs per wave: cooperative IK */
 __device__ __forceinline__ void action_body(const DevModel* __restrict__ m, float* __restrict__ state, const float* __restrict__ action,
-                                            float* __restrict__ target_poses, int env0, int N, const int* __restrict__ member, const int bid) {
+                                            float* __restrict__ target_poses, int env0, int N, const int* __restrict__ member, const int bid,
+                                            float* __restrict__ raw = nullptr) {
   const int l16 = threadIdx.x & 15;
   const int env_raw = env0 + bid * (blockDim.x >> 4) + (threadIdx.x >> 4);      /* this launch covers places [env0, N) of its group; one env per DPP row */
   const bool live = env_raw < N;
@@ -3600,6 +3601,9 @@ __device__ __forceinline__ void action_body(const DevModel* __restrict__ m, floa
     else { for (int rep = 0; rep < 4; rep++) qj = ik_coop<7>(m, tpos, tq, qj, 20, l16, live, &ik_capped, &ik_marginal); }
   }
   if (!live) return;
+  /* k_debug_action only (the step's kernels pass no raw): the solution before the two clamps, [env][0..6], and at [env][7] 1 * capped + 2 * marginal + 4 * place (the
+   * env's position in the member table: which row of which block it ran in) */
+  if (raw && l16 < 8) raw[(size_t)env * 8 + l16] = l16 < nd ? qj : (l16 == 7 ? (float)((ik_capped ? 1 : 0) | (ik_marginal ? 2 : 0) | (place << 2)) : 0.f);
   if (l16 < nd) {
     float t = clampf(qj, m->ll[l16], m->ul[l16]);
     t = clampf(t, q0 - m->inc[l16], q0 + m->inc[l16]);
@@ -3627,6 +3631,11 @@ __device__ __forceinline__ void action_body(const DevModel* __restrict__ m, floa
 __global__ void __launch_bounds__(64) k_action(const DevModel* __restrict__ m, float* __restrict__ state, const float* __restrict__ action,
                                               float* __restrict__ target_poses, int env0, int N, const int* __restrict__ member) {
   action_body(m, state, action, target_poses, env0, N, member, blockIdx.x);
+}
+/* rp_debug_action: k_action's body and launch shape, with the unclamped solution and the IK's two flags written out as well (tests/test_gpu_action.py) */
+__global__ void __launch_bounds__(64) k_debug_action(const DevModel* __restrict__ m, float* __restrict__ state, const float* __restrict__ action, int env0, int N,
+                                                    const int* __restrict__ member, float* __restrict__ raw) {
+  action_body(m, state, action, nullptr, env0, N, member, blockIdx.x, raw);
 }
 
 __device__ __forceinline__ void copy_out(float* __restrict__ dst, const float* src, int nfloat, int lane) {

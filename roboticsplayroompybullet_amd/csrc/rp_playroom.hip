@@ -507,6 +507,25 @@ int rp_reset_goal(rp_handle h, const float* goal, const uint8_t* mask, void* str
   return RP_OK;
 }
 
+/* the split pipeline's G env groups: places [b[g], b[g + 1]) of the load ranking */
+static GroupBounds split_groups(rp_handle h, int G, int N) {
+  GroupBounds gb;
+  long long tot = 0, acc = 0;
+  static const int split3[3] = {25, 35, 40};     /* default for 3 groups: the heavy group smaller (2.54 vs 2.59 ms per step, equal thirds) */
+  const int* split = h->gsplit;
+  if (h->gsplit[0] <= 0 && G == 3) split = split3;
+  for (int g = 0; g < G; g++) tot += split[g] > 0 ? split[g] : 0;
+  bool custom = tot > 0;
+  for (int g = 0; g < G && custom; g++) if (split[g] <= 0) custom = false;
+  gb.b[0] = 0;
+  for (int g = 0; g < G; g++) {
+    acc += custom ? split[g] : 1;
+    gb.b[g + 1] = (int)((long long)N * acc / (custom ? tot : G));
+  }
+  for (int g = G + 1; g <= RP_MAX_GROUPS; g++) gb.b[g] = N;
+  return gb;
+}
+
 int rp_step(rp_handle h, const float* action, const rp_out* out, void* stream) {
   if (!h || !action) { if (h) snprintf(h->err, 256, "rp_step: action is NULL"); return RP_ERR_ARG; }
   DevGuard guard(h->cfg.device);
@@ -553,22 +572,7 @@ int rp_step(rp_handle h, const float* action, const rp_out* out, void* stream) {
 #define TIMED(launch) do { if (ev) hipEventRecord(ev[e++], gs); launch; if (ev) hipEventRecord(ev[e++], gs); } while (0)
 #endif
     /* groups by load: rank all envs by the load class of the latest k_solve2 and cut the ranking into the G groups */
-    GroupBounds gb;
-    {
-      long long tot = 0, acc = 0;
-      static const int split3[3] = {25, 35, 40};     /* default for 3 groups: the heavy group smaller (2.54 vs 2.59 ms per step, equal thirds) */
-      const int* split = h->gsplit;
-      if (h->gsplit[0] <= 0 && G == 3) split = split3;
-      for (int g = 0; g < G; g++) tot += split[g] > 0 ? split[g] : 0;
-      bool custom = tot > 0;
-      for (int g = 0; g < G && custom; g++) if (split[g] <= 0) custom = false;
-      gb.b[0] = 0;
-      for (int g = 0; g < G; g++) {
-        acc += custom ? split[g] : 1;
-        gb.b[g + 1] = (int)((long long)N * acc / (custom ? tot : G));
-      }
-      for (int g = G + 1; g <= RP_MAX_GROUPS; g++) gb.b[g] = N;
-    }
+    const GroupBounds gb = split_groups(h, G, N);
     const int* member = h->member[h->member_cur];
     if (h->sort_G == 0) {
       hipLaunchKernelGGL(k_member_identity, dim3((N + 255) / 256), dim3(256), 0, s, h->member[h->member_cur], N, h->hv_cnt);
@@ -1064,6 +1068,32 @@ int rp_debug_substep(rp_handle h, int32_t env, float* host_buf) {
   hipLaunchKernelGGL(k_debug_substep, dim3(N), dim3(64), 0, 0, h->dev_model, h->state, h->dbg, N, env);
   HIPCHK(h, hipDeviceSynchronize());
   HIPCHK(h, hipMemcpy(host_buf, h->dbg, 4096 * sizeof(float), hipMemcpyDeviceToHost));
+  return RP_OK;
+}
+
+/* test hook: the action stage alone (k_action's body in k_action's launch shape) on the current state, on the NULL stream.  The envs are cut into blocks by the LATEST step's
+ * member table and group bounds as they stand (the next step would re-rank first); before the first step of a pipeline, in identity order and rp_set_groups' groups.
+ * raw_dev [N][8]: the solution before the clamps to the joint limits and to q +- inc (7), then 1 * capped + 2 * marginal + 4 * place.  Motor targets and status word go
+ * into the state as in a step; nothing else is written.  Synchronises the stream. */
+int rp_debug_action(rp_handle h, const float* action_dev, float* raw_dev) {
+  if (!h || !action_dev || !raw_dev) { if (h) snprintf(h->err, 256, "rp_debug_action: action_dev or raw_dev is NULL"); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  const int N = h->cfg.num_envs;
+  int G = h->sort_G;
+  GroupBounds gb = h->gb;
+  const int* member = h->member[h->member_cur];
+  if (G == 0) {
+    G = h->fused == 0 ? h->groups : 1;
+    if (G > (N + 63) / 64) G = (N + 63) / 64;
+    gb = split_groups(h, G, N);
+    member = nullptr;
+  }
+  for (int g = 0; g < G; g++) {
+    const int e0 = gb.b[g], e1 = gb.b[g + 1];
+    if (e1 > e0) hipLaunchKernelGGL(k_debug_action, dim3((e1 - e0 + 3) / 4), dim3(64), 0, 0, h->dev_model, h->state, action_dev, e0, e1, member, raw_dev);
+  }
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(0));
   return RP_OK;
 }
 

@@ -862,6 +862,19 @@ class VecPlayEnv:
         _lib.check(self.lib, self.h, self.lib.rp_get_timers(self.h, C.byref(t)), 'rp_get_timers')
         return {n: getattr(t, n) for n, _ in _lib.RpTimers._fields_}
 
+    def debug_action(self, actions, places=False):
+        """test hook: the action stage alone on the current state (rp_debug_action).  Returns (raw [N, 7] float32: the joint solution before the clamps to the joint
+        limits and to q +- inc, flags [N] int32: 1 = the last IK call ran out of iterations (status bit 8), 2 = a stopping test was marginal (bit 16)) and, with
+        places=True, every env's place [N] int32 in the member table the launch went by; the motor targets and the status word are left in the state as a step
+        leaves them (get_state)."""
+        a = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        assert a.shape == (self.num_envs, self.dims['action']), a.shape
+        raw = torch.empty((self.num_envs, 8), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()      # (the hook runs on the NULL stream)
+        _lib.check(self.lib, self.h, self.lib.rp_debug_action(self.h, C.c_void_p(a.data_ptr()), C.c_void_p(raw.data_ptr())), 'rp_debug_action')
+        word = raw[:, 7].to(torch.int32)
+        return (raw[:, :7].contiguous(), word & 3) + ((word >> 2,) if places else ())
+
     def debug_substep(self, env=0):
         buf = (C.c_float * 4096)()
         _lib.check(self.lib, self.h, self.lib.rp_debug_substep(self.h, env, buf), 'rp_debug_substep')
