@@ -3433,40 +3433,41 @@ __global__ void k_read_state(float* __restrict__ dst, const float* __restrict__ 
   dst[i] = k < RP_REC_FLOATS ? rec[env * RP_REC_FLOATS + k] : cache[env * nc + (k - RP_REC_FLOATS)];
 }
 
-/* per-env dynamics table (rp_set_dynamics / rp_get_dynamics): thread per table entry.  fr [rows][no] / ms [rows][nf] (nullptr: leave those columns), rows 1 = every
- * env the same row; only envs whose mask byte is non-zero (mask nullptr: all) */
+/* per-env parameter tables (rp_set_ / rp_get_ dynamics, wrench, actuation): a table is [N][W] floats whose row is up to three column blocks side by side (dynamics:
+ * friction[no] mass[nf]; wrench: one block; actuation: gravity[3] motor_gain[na] motor_strength[na]), and the caller has one array [rows][w] per block.  TabCols carries
+ * the arrays and widths by value; a width may be 0 (a model without a free body) and such a block is stepped over, never indexed */
+template <typename T> struct TabCols { T* p0; T* p1; T* p2; int w0, w1, w2; };
 static_assert(RP_MAX_OBJ + RP_MAX_FREE <= 64, "stage_dynamics: one entry of the row per thread of a wave");
-__global__ void k_set_dynamics(float* __restrict__ dyn, const float* __restrict__ fr, const float* __restrict__ ms, int rows, const uint8_t* __restrict__ mask,
-                               int N, int no, int nf) {
-  const size_t W = (size_t)(no + nf);
+/* thread per table entry.  rows 1 = every env the same row; only envs whose mask byte is non-zero (mask nullptr: all); a nullptr source leaves its columns alone, or with
+ * null_is_zero (the wrench table) zeroes them */
+__global__ void k_set_table(float* __restrict__ tab, TabCols<const float> c, int null_is_zero, int rows, const uint8_t* __restrict__ mask, int N) {
+  const size_t W = (size_t)(c.w0 + c.w1 + c.w2);
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)N * W) return;
-  const size_t env = i / W, k = i % W, r = rows == 1 ? 0 : env;
+  const size_t env = i / W, r = rows == 1 ? 0 : env;
+  int k = (int)(i % W), w = c.w0;
   if (mask && !mask[env]) return;
-  if (k < (size_t)no) { if (fr) dyn[i] = fr[r * no + k]; }
-  else if (ms) dyn[i] = ms[r * nf + (k - no)];
+  const float* src = c.p0;
+  if (k >= c.w0) {
+    k -= c.w0; src = c.p1; w = c.w1;
+    if (k >= c.w1) { k -= c.w1; src = c.p2; w = c.w2; }
+  }
+  if (src) tab[i] = src[r * w + k];
+  else if (null_is_zero) tab[i] = 0.f;
 }
-__global__ void k_get_dynamics(const float* __restrict__ dyn, float* __restrict__ fr, float* __restrict__ ms, int N, int no, int nf) {
-  const size_t W = (size_t)(no + nf);
+/* thread per table entry; a nullptr destination is skipped */
+__global__ void k_get_table(const float* __restrict__ tab, TabCols<float> c, int N) {
+  const size_t W = (size_t)(c.w0 + c.w1 + c.w2);
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)N * W) return;
-  const size_t env = i / W, k = i % W;
-  if (k < (size_t)no) { if (fr) fr[env * no + k] = dyn[i]; }
-  else if (ms) ms[env * nf + (k - no)] = dyn[i];
-}
-
-/* per-env wrench table (rp_set_wrench / rp_get_wrench): thread per table entry.  src [rows][W] (nullptr: zeros), rows 1 = every env the same row; only envs whose
- * mask byte is non-zero (mask nullptr: all) */
-__global__ void k_set_wrench(float* __restrict__ tab, const float* __restrict__ src, int rows, const uint8_t* __restrict__ mask, int N, int W) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)N * W) return;
-  const size_t env = i / W, k = i % W;
-  if (mask && !mask[env]) return;
-  tab[i] = src ? src[(rows == 1 ? 0 : env) * W + k] : 0.f;
-}
-__global__ void k_get_wrench(const float* __restrict__ tab, float* __restrict__ dst, size_t total) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < total) dst[i] = tab[i];
+  const size_t env = i / W;
+  int k = (int)(i % W), w = c.w0;
+  float* dst = c.p0;
+  if (k >= c.w0) {
+    k -= c.w0; dst = c.p1; w = c.w1;
+    if (k >= c.w1) { k -= c.w1; dst = c.p2; w = c.w2; }
+  }
+  if (dst) dst[env * w + k] = tab[i];
 }
 
 /* per-env kinematics (rp_set_kinematics / rp_get_kinematics): thread per word.  A pos row is arm q[na], per free body x y z qx qy qz qw, scene-joint q[nj]; a vel row
@@ -3536,31 +3537,6 @@ __global__ void k_copy_envs_gather(float4* __restrict__ rec, float4* __restrict_
   const float4 v = stage[(size_t)s * W + k];
   if (k < R4) rec[env * R4 + k] = v; else cache[env * nc4 + (k - R4)] = v;
   if (k == 0 && copy_steps) ep_steps[env] = steps_stage[s];
-}
-
-/* per-env actuation table (rp_set_actuation / rp_get_actuation): thread per table entry; the row is gravity[3], motor_gain[na], motor_strength[na].  Sources [rows][3] /
- * [rows][na] / [rows][na], rows 1 = every env the same row, a nullptr source leaves its columns alone; only envs whose mask byte is non-zero (mask nullptr: all) */
-__global__ void k_set_actuation(float* __restrict__ tab, const float* __restrict__ gr, const float* __restrict__ gn, const float* __restrict__ sg, int rows,
-                                const uint8_t* __restrict__ mask, int N, int na) {
-  const int W = 3 + 2 * na;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)N * W) return;
-  const size_t env = i / W, r = rows == 1 ? 0 : env;
-  const int k = (int)(i % W);
-  if (mask && !mask[env]) return;
-  if (k < 3) { if (gr) tab[i] = gr[r * 3 + k]; }
-  else if (k < 3 + na) { if (gn) tab[i] = gn[r * na + (k - 3)]; }
-  else if (sg) tab[i] = sg[r * na + (k - 3 - na)];
-}
-__global__ void k_get_actuation(const float* __restrict__ tab, float* __restrict__ gr, float* __restrict__ gn, float* __restrict__ sg, int N, int na) {
-  const int W = 3 + 2 * na;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)N * W) return;
-  const size_t env = i / W;
-  const int k = (int)(i % W);
-  if (k < 3) { if (gr) gr[env * 3 + k] = tab[i]; }
-  else if (k < 3 + na) { if (gn) gn[env * na + (k - 3)] = tab[i]; }
-  else if (sg) sg[env * na + (k - 3 - na)] = tab[i];
 }
 
 /* ------------------------------------------------------------------ split pipeline for rp_step

@@ -92,6 +92,35 @@ struct DevGuard {
   ~DevGuard() { if (prev >= 0 && prev != cur) (void)hipSetDevice(prev); }
 };
 
+/* the one path of the per-env parameter tables (dynamics, wrench, actuation; k_set_table / k_get_table): rows_ok is the `rows` check every set entry point makes,
+ * launch_table_set the bare launch over table [num_envs][c.w0 + c.w1 + c.w2] (rp_create fills its default rows with it), table_set / table_get an entry point's
+ * checked launch on `stream` */
+static bool rows_ok(rp_sim* h, const char* fn, int32_t rows) {
+  if (rows == 1 || rows == h->cfg.num_envs) return true;
+  snprintf(h->err, 256, "%s: rows = %d, expected 1 or num_envs = %d", fn, rows, h->cfg.num_envs);
+  return false;
+}
+static void launch_table_set(rp_sim* h, float* tab, TabCols<const float> c, int null_is_zero, int rows, const uint8_t* mask, void* stream) {
+  const int N = h->cfg.num_envs;
+  const size_t total = (size_t)N * (c.w0 + c.w1 + c.w2);
+  hipLaunchKernelGGL(k_set_table, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tab, c, null_is_zero, rows, mask, N);
+}
+static int table_set(rp_sim* h, const char* fn, float* tab, TabCols<const float> c, int null_is_zero, int32_t rows, const uint8_t* mask, void* stream) {
+  if (!rows_ok(h, fn, rows)) return RP_ERR_ARG;
+  DevGuard guard(h->cfg.device);
+  launch_table_set(h, tab, c, null_is_zero, (int)rows, mask, stream);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+static int table_get(rp_sim* h, const float* tab, TabCols<float> c, void* stream) {
+  DevGuard guard(h->cfg.device);
+  const int N = h->cfg.num_envs;
+  const size_t total = (size_t)N * (c.w0 + c.w1 + c.w2);
+  hipLaunchKernelGGL(k_get_table, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tab, c, N);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
 static OutPtrs to_ptrs(const rp_out* o) {
   OutPtrs p;
   memset(&p, 0, sizeof(p));
@@ -305,8 +334,7 @@ int rp_create(const rp_config* cfg, rp_handle* out) {
     CREATE_CHK(hipMalloc((void**)&h->dyn, (size_t)(N + 1) * nd * sizeof(float)));      /* (+ one row behind the table: the bake's, broadcast from there) */
     const float* base = h->dyn + (size_t)N * nd;
     CREATE_CHK(hipMemcpy((void*)base, row, nd * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_set_dynamics, dim3((unsigned)(((size_t)N * nd + 255) / 256)), dim3(256), 0, 0, h->dyn, base, base + d->n_obj, 1, (const uint8_t*)nullptr, N,
-                       d->n_obj, d->n_free);
+    launch_table_set(h, h->dyn, {base, base + d->n_obj, nullptr, d->n_obj, d->n_free, 0}, 0, 1, nullptr, nullptr);
     CREATE_CHK(hipGetLastError());
     d->dyn = h->dyn;
   }
@@ -324,7 +352,7 @@ int rp_create(const rp_config* cfg, rp_handle* out) {
     CREATE_CHK(hipMalloc((void**)&h->act, (size_t)(N + 1) * W * sizeof(float)));      /* (+ one row behind the table: the default row, broadcast from there) */
     const float* base = h->act + (size_t)N * W;
     CREATE_CHK(hipMemcpy((void*)base, row, W * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_set_actuation, dim3((unsigned)(((size_t)N * W + 255) / 256)), dim3(256), 0, 0, h->act, base, base + 3, base + 3 + na, 1, (const uint8_t*)nullptr, N, na);
+    launch_table_set(h, h->act, {base, base + 3, base + 3 + na, 3, na, na}, 0, 1, nullptr, nullptr);
     CREATE_CHK(hipGetLastError());
     d->act = h->act;
   }
@@ -740,25 +768,13 @@ int rp_get_dynamics_dims(rp_handle h, int32_t* n_obj, int32_t* n_free) {
 /* enqueued on `stream` like a step: a step queued after it on the same stream sees the new values, one queued before it the old ones */
 int rp_set_dynamics(rp_handle h, const float* friction, const float* mass, int32_t rows, const uint8_t* mask, void* stream) {
   if (!h) return RP_ERR_ARG;
-  const int N = h->cfg.num_envs, no = h->host_model.n_obj, nf = h->host_model.n_free;
   if (!friction && !mass) { snprintf(h->err, 256, "rp_set_dynamics: friction and mass are both NULL"); return RP_ERR_ARG; }
-  if (rows != 1 && rows != N) { snprintf(h->err, 256, "rp_set_dynamics: rows = %d, expected 1 or num_envs = %d", rows, N); return RP_ERR_ARG; }
-  DevGuard guard(h->cfg.device);
-  const size_t total = (size_t)N * (no + nf);
-  hipLaunchKernelGGL(k_set_dynamics, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->dyn, friction, mass, (int)rows, mask, N, no,
-                     nf);
-  HIPCHK(h, hipGetLastError());
-  return RP_OK;
+  return table_set(h, "rp_set_dynamics", h->dyn, {friction, mass, nullptr, h->host_model.n_obj, h->host_model.n_free, 0}, 0, rows, mask, stream);
 }
 
 int rp_get_dynamics(rp_handle h, float* friction, float* mass, void* stream) {
   if (!h || (!friction && !mass)) { if (h) snprintf(h->err, 256, "rp_get_dynamics: friction and mass are both NULL"); return RP_ERR_ARG; }
-  DevGuard guard(h->cfg.device);
-  const int N = h->cfg.num_envs, no = h->host_model.n_obj, nf = h->host_model.n_free;
-  const size_t total = (size_t)N * (no + nf);
-  hipLaunchKernelGGL(k_get_dynamics, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->dyn, friction, mass, N, no, nf);
-  HIPCHK(h, hipGetLastError());
-  return RP_OK;
+  return table_get(h, h->dyn, {friction, mass, nullptr, h->host_model.n_obj, h->host_model.n_free, 0}, stream);
 }
 
 int rp_get_wrench_dims(rp_handle h, int32_t* n_arm, int32_t* n_free, int32_t* n_j1) {
@@ -770,22 +786,12 @@ int rp_get_wrench_dims(rp_handle h, int32_t* n_arm, int32_t* n_free, int32_t* n_
 /* enqueued on `stream` like rp_set_dynamics: a step queued after it on the same stream feels the new wrenches from its first substep, one queued before it the old ones */
 int rp_set_wrench(rp_handle h, const float* wrench, int32_t rows, const uint8_t* mask, void* stream) {
   if (!h) return RP_ERR_ARG;
-  const int N = h->cfg.num_envs, W = 6 * (h->host_model.nbody - 1);
-  if (rows != 1 && rows != N) { snprintf(h->err, 256, "rp_set_wrench: rows = %d, expected 1 or num_envs = %d", rows, N); return RP_ERR_ARG; }
-  DevGuard guard(h->cfg.device);
-  const size_t total = (size_t)N * W;
-  hipLaunchKernelGGL(k_set_wrench, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->wrench, wrench, (int)rows, mask, N, W);
-  HIPCHK(h, hipGetLastError());
-  return RP_OK;
+  return table_set(h, "rp_set_wrench", h->wrench, {wrench, nullptr, nullptr, 6 * (h->host_model.nbody - 1), 0, 0}, 1, rows, mask, stream);      /* (NULL = zeros) */
 }
 
 int rp_get_wrench(rp_handle h, float* wrench, void* stream) {
   if (!h || !wrench) { if (h) snprintf(h->err, 256, "rp_get_wrench: wrench is NULL"); return RP_ERR_ARG; }
-  DevGuard guard(h->cfg.device);
-  const size_t total = (size_t)h->cfg.num_envs * 6 * (h->host_model.nbody - 1);
-  hipLaunchKernelGGL(k_get_wrench, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->wrench, wrench, total);
-  HIPCHK(h, hipGetLastError());
-  return RP_OK;
+  return table_get(h, h->wrench, {wrench, nullptr, nullptr, 6 * (h->host_model.nbody - 1), 0, 0}, stream);
 }
 
 int rp_get_actuation_dims(rp_handle h, int32_t* n_arm) {
@@ -797,25 +803,15 @@ int rp_get_actuation_dims(rp_handle h, int32_t* n_arm) {
 /* enqueued on `stream` like rp_set_dynamics: a step queued after it on the same stream runs under the new values from its first substep, one queued before it under the old ones */
 int rp_set_actuation(rp_handle h, const float* gravity, const float* motor_gain, const float* motor_strength, int32_t rows, const uint8_t* mask, void* stream) {
   if (!h) return RP_ERR_ARG;
-  const int N = h->cfg.num_envs, na = h->host_model.n_arm;
+  const int na = h->host_model.n_arm;
   if (!gravity && !motor_gain && !motor_strength) { snprintf(h->err, 256, "rp_set_actuation: gravity, motor_gain and motor_strength are all NULL"); return RP_ERR_ARG; }
-  if (rows != 1 && rows != N) { snprintf(h->err, 256, "rp_set_actuation: rows = %d, expected 1 or num_envs = %d", rows, N); return RP_ERR_ARG; }
-  DevGuard guard(h->cfg.device);
-  const size_t total = (size_t)N * (3 + 2 * na);
-  hipLaunchKernelGGL(k_set_actuation, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->act, gravity, motor_gain, motor_strength, (int)rows, mask,
-                     N, na);
-  HIPCHK(h, hipGetLastError());
-  return RP_OK;
+  return table_set(h, "rp_set_actuation", h->act, {gravity, motor_gain, motor_strength, 3, na, na}, 0, rows, mask, stream);
 }
 
 int rp_get_actuation(rp_handle h, float* gravity, float* motor_gain, float* motor_strength, void* stream) {
   if (!h || (!gravity && !motor_gain && !motor_strength)) { if (h) snprintf(h->err, 256, "rp_get_actuation: gravity, motor_gain and motor_strength are all NULL"); return RP_ERR_ARG; }
-  DevGuard guard(h->cfg.device);
-  const int N = h->cfg.num_envs, na = h->host_model.n_arm;
-  const size_t total = (size_t)N * (3 + 2 * na);
-  hipLaunchKernelGGL(k_get_actuation, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)h->act, gravity, motor_gain, motor_strength, N, na);
-  HIPCHK(h, hipGetLastError());
-  return RP_OK;
+  const int na = h->host_model.n_arm;
+  return table_get(h, h->act, {gravity, motor_gain, motor_strength, 3, na, na}, stream);
 }
 
 /* enqueued on `stream` like rp_set_wrench; writes the named words of the state records (and, with RP_KIN_CLEAR_CONTACTS, zeroes the cache rows) and nothing else */
@@ -823,7 +819,7 @@ int rp_set_kinematics(rp_handle h, const float* pos, const float* vel, int32_t r
   if (!h) return RP_ERR_ARG;
   const int N = h->cfg.num_envs, na = h->host_model.n_arm, nf = h->host_model.n_free, nj = h->host_model.n_j1;
   if (!pos && !vel) { snprintf(h->err, 256, "rp_set_kinematics: pos and vel are both NULL"); return RP_ERR_ARG; }
-  if (rows != 1 && rows != N) { snprintf(h->err, 256, "rp_set_kinematics: rows = %d, expected 1 or num_envs = %d", rows, N); return RP_ERR_ARG; }
+  if (!rows_ok(h, "rp_set_kinematics", rows)) return RP_ERR_ARG;
   if (flags & ~(uint32_t)RP_KIN_CLEAR_CONTACTS) { snprintf(h->err, 256, "rp_set_kinematics: unknown bits in flags (0x%x)", flags); return RP_ERR_ARG; }
   DevGuard guard(h->cfg.device);
   const int nclr = (flags & RP_KIN_CLEAR_CONTACTS) && h->pmcache ? PMC_FLOATS : 0;

@@ -5,6 +5,7 @@ is a [N, ...] torch tensor on the env's device.  State lives inside the HIP libr
 step()/reset() are owned by this object and overwritten by the next call (clone to keep).
 """
 import ctypes as C
+import functools
 import json
 import math
 import os
@@ -36,12 +37,52 @@ _SCENE_NAMES = {'complex_scene': {0: 'floor', 1: 'door', 6: 'drawer', 7: 'dial',
                 'push_scene': {0: 'floor', 1: 'tray', 2: 'block'}, 'default_scene': {0: 'floor'}}
 
 
+@functools.lru_cache(maxsize=None)
+def _bake():
+    """the models of assets/models.json, read once per process"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets', 'models.json')) as f:
+        return json.load(f)['models']
+
+
+def _model(kind):
+    return next(m for m in _bake() if m['kind'] == kind)
+
+
+def _per_model(names):
+    """names(model) worked out once per model.  The tuples it holds are shared; a dict of them is handed out as a fresh dict, so callers may change what they get"""
+    cached = functools.lru_cache(maxsize=None)(names)
+
+    @functools.wraps(names)
+    def fresh(model):
+        v = cached(model)
+        return dict(v) if isinstance(v, dict) else v
+    return fresh
+
+
+def _check_values(what, v, lo=None, hi=None, problem=None):
+    """a host-side value (number, sequence, numpy array, CPU tensor) as a float32 CPU tensor: every entry finite, inside [lo, hi] where given, and problem(t), where
+    given, finds nothing to say (it returns the complaint) - ValueError otherwise"""
+    t = torch.as_tensor(v, dtype=torch.float32, device='cpu')
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError('%s: values must be finite' % what)
+    if lo is not None and not bool(((t >= lo) & (t <= hi)).all()):
+        raise ValueError('%s: values must lie in [%g, %g]' % (what, lo, hi))
+    complaint = problem(t) if problem is not None else None
+    if complaint:
+        raise ValueError(complaint)
+    return t
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+@_per_model
 def dynamics_names(model):
     """{'friction': names of the collision objects, 'mass': names of the free bodies} of a baked model ('U', 'R', 'P', 'Q', 'V', 'W'), in the column
     order of rp_get_dynamics: objects by their bake number (col_obj), free bodies in the record's order.  Arm links are named by their Bullet link
     index ('link7'), the arm's fixed base 'arm_base', scene bodies as _SCENE_NAMES has them."""
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets', 'models.json')) as f:
-        mdl = next(m for m in json.load(f)['models'] if m['kind'] == model)
+    mdl = _model(model)
     scene = _SCENE_NAMES[mdl['scene']]
     jointed = {j['scene_id'] for j in mdl['joint1']}
 
@@ -67,22 +108,17 @@ def dynamics_names(model):
 def check_dynamics_values(what, v):
     """a host-side friction / mass value (number, sequence, numpy array, CPU tensor) as a float32 CPU tensor; friction must be >= 0, mass > 0, both
     finite (ValueError otherwise)"""
-    t = torch.as_tensor(v, dtype=torch.float32, device='cpu')
-    if not bool(torch.isfinite(t).all()):
-        raise ValueError('%s: values must be finite' % what)
-    if what == 'mass' and not bool((t > 0).all()):
-        raise ValueError('mass: values must be > 0')
-    if what == 'friction' and not bool((t >= 0).all()):
-        raise ValueError('friction: values must be >= 0')
-    return t
+    rule = {'mass': lambda t: None if bool((t > 0).all()) else 'mass: values must be > 0',
+            'friction': lambda t: None if bool((t >= 0).all()) else 'friction: values must be >= 0'}
+    return _check_values(what, v, problem=rule.get(what))
 
 
+@_per_model
 def wrench_names(model):
     """names of the moving bodies of a baked model, in the column order of rp_get_wrench: the arm's links by their Bullet link index ('link7', one per
     dof, in dof order), the free bodies as dynamics_names' 'mass' calls them ('block', 'drawer', ...), the scene-joint bodies by their scene name
     ('door', 'button', 'dial')"""
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets', 'models.json')) as f:
-        mdl = next(m for m in json.load(f)['models'] if m['kind'] == model)
+    mdl = _model(model)
     scene = _SCENE_NAMES[mdl['scene']]
     names = ['link%d' % a['bullet_index'] for a in mdl['arm']] + list(dynamics_names(model)['mass']) + \
         [scene.get(j['scene_id'], 'joint1_%d' % j['scene_id']) for j in mdl['joint1']]
@@ -92,18 +128,15 @@ def wrench_names(model):
 
 def check_wrench_values(v):
     """a host-side wrench (sequence, numpy array, CPU tensor) as a float32 CPU tensor; every value finite (ValueError otherwise)"""
-    t = torch.as_tensor(v, dtype=torch.float32, device='cpu')
-    if not bool(torch.isfinite(t).all()):
-        raise ValueError('wrench: values must be finite')
-    return t
+    return _check_values('wrench', v)
 
 
+@_per_model
 def kinematics_names(model):
     """{'pos': column names of rp_get_kinematics' pos, 'vel': of its vel} of a baked model.  Both start with the arm's dofs as wrench_names names their links
     ('link7', in dof order) and end with the scene joints ('door', 'button', 'dial'); between them every free body of wrench_names has seven pos columns
     ('block.x', '.y', '.z', '.qx', '.qy', '.qz', '.qw') and six vel columns ('block.vx', '.vy', '.vz', '.wx', '.wy', '.wz': world coordinates)"""
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets', 'models.json')) as f:
-        mdl = next(m for m in json.load(f)['models'] if m['kind'] == model)
+    mdl = _model(model)
     names = wrench_names(model)
     na, nf = mdl['n_arm'], len(mdl['free'])
     arm, free, j1 = list(names[:na]), names[na:na + nf], list(names[na + nf:])
@@ -117,25 +150,21 @@ def check_kinematics_values(what, v, names):
     """a host-side pos / vel value (sequence, numpy array, CPU tensor; the last axis runs over `names`, a run of kinematics_names columns) as a float32 CPU
     tensor; every value finite and every quaternion (the four columns from a '.qx' name on) within 1e-3 of unit norm - the library writes the words
     verbatim (ValueError otherwise)"""
-    t = torch.as_tensor(v, dtype=torch.float32, device='cpu')
-    if not bool(torch.isfinite(t).all()):
-        raise ValueError('%s: values must be finite' % what)
-    if t.dim() == 0 or t.shape[-1] != len(names):
-        raise ValueError('%s: the last axis has %s entries, expected %d' % (what, t.shape[-1] if t.dim() else 'no', len(names)))
-    for k, nm in enumerate(names):
-        if nm.endswith('.qx'):
-            nrm = t[..., k:k + 4].double().norm(dim=-1)
-            if not bool(((nrm - 1.0).abs() <= 1e-3).all()):
-                raise ValueError('%s: the quaternion %s .. qw must have norm 1 within 1e-3' % (what, nm))
-    return t
+    def problem(t):
+        if t.dim() == 0 or t.shape[-1] != len(names):
+            return '%s: the last axis has %s entries, expected %d' % (what, t.shape[-1] if t.dim() else 'no', len(names))
+        for k, nm in enumerate(names):
+            if nm.endswith('.qx') and not bool(((t[..., k:k + 4].double().norm(dim=-1) - 1.0).abs() <= 1e-3).all()):
+                return '%s: the quaternion %s .. qw must have norm 1 within 1e-3' % (what, nm)
+
+    return _check_values(what, v, problem=problem)
 
 
+@_per_model
 def actuation_names(model):
     """{'gravity': ['x', 'y', 'z'], 'motor': the arm's dofs as wrench_names calls their links ('link7', in dof order)} of a baked model: the columns of
     rp_get_actuation's gravity and of its motor_gain / motor_strength"""
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'assets', 'models.json')) as f:
-        mdl = next(m for m in json.load(f)['models'] if m['kind'] == model)
-    return {'gravity': ('x', 'y', 'z'), 'motor': tuple('link%d' % a['bullet_index'] for a in mdl['arm'])}
+    return {'gravity': ('x', 'y', 'z'), 'motor': tuple('link%d' % a['bullet_index'] for a in _model(model)['arm'])}
 
 
 ACTUATION_RANGES = {'gravity': (-50.0, 50.0), 'motor_gain': (0.0, 10.0), 'motor_strength': (0.0, 10.0)}
@@ -145,13 +174,7 @@ def check_actuation_values(what, v):
     """a host-side gravity / motor_gain / motor_strength value (sequence, numpy array, CPU tensor) as a float32 CPU tensor; finite and inside
     ACTUATION_RANGES (|g| <= 50 per component; 0 <= gain <= 10, which keeps the motor's position gain 0.1 * gain <= 1; 0 <= strength <= 10),
     ValueError otherwise"""
-    t = torch.as_tensor(v, dtype=torch.float32, device='cpu')
-    lo, hi = ACTUATION_RANGES[what]
-    if not bool(torch.isfinite(t).all()):
-        raise ValueError('%s: values must be finite' % what)
-    if not bool(((t >= lo) & (t <= hi)).all()):
-        raise ValueError('%s: values must lie in [%g, %g]' % (what, lo, hi))
-    return t
+    return _check_values(what, v, *ACTUATION_RANGES[what])
 
 
 class VecPlayEnv:
@@ -219,6 +242,8 @@ class VecPlayEnv:
         cfg.flags = flags
         self.h = C.c_void_p()
         self._done = None
+        self._table_dims = {}      # _dims_of's answers
+        self._kept = {}      # entry point -> the tensors its latest call handed to the library: the kernel reads them when the stream gets there
         _lib.check(self.lib, None, self.lib.rp_create(C.byref(cfg), C.byref(self.h)), 'rp_create')
         d = _lib.RpDims()
         self.lib.rp_get_dims(self.h, C.byref(d))
@@ -255,7 +280,7 @@ class VecPlayEnv:
             limit = self._max_episode_steps if max_episode_steps is None else int(max_episode_steps)
             self.max_episode_steps = limit if limit and limit > 0 else None
             when = _lib.AR_TIME_LIMIT | (_lib.AR_FAULT if end_on_fault else 0) | (_lib.AR_SUCCESS if end_on_success else 0)
-            _lib.check(self.lib, self.h, self.lib.rp_set_autoreset(self.h, self.max_episode_steps or 0, when), 'rp_set_autoreset')
+            self._call('rp_set_autoreset', self.max_episode_steps or 0, when)
             # the ended envs' step rows (info['terminal_observation']) and the done reasons, owned like buf: overwritten by the next step
             self.final = {k: f(self.dims[k]) for k in OBS_KEYS}
             self.final['gripper_proprioception'] = torch.zeros(N, dtype=torch.int32, device=dev)
@@ -268,6 +293,10 @@ class VecPlayEnv:
             if not self.autoreset:
                 raise ValueError('reset_table needs VecPlayEnv(..., autoreset=True)')
             self.set_reset_table(reset_table)
+
+    def _call(self, fn, *args):
+        """self.lib.<fn>(handle, *args); a non-zero return raises RuntimeError with rp_last_error's text"""
+        _lib.check(self.lib, self.h, getattr(self.lib, fn)(self.h, *args), fn)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -314,15 +343,14 @@ class VecPlayEnv:
         mp = None
         if mask is not None:
             mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mp = C.c_void_p(mask.data_ptr())
+            mp = _ptr(mask)
         self._flip_pack(keep_rows=mask is not None)
         if o is None:
-            _lib.check(self.lib, self.h, self.lib.rp_reset(self.h, mp, C.byref(self.out), self._stream()), 'rp_reset')
+            self._call('rp_reset', mp, C.byref(self.out), self._stream())
         else:
             o = o.to(device=self.device, dtype=torch.float32).contiguous()
             assert o.dim() == 2 and o.shape[0] == self.num_envs, o.shape
-            _lib.check(self.lib, self.h, self.lib.rp_reset_to(self.h, C.c_void_p(o.data_ptr()), o.shape[1], mp, C.byref(self.out), self._stream()),
-                       'rp_reset_to')
+            self._call('rp_reset_to', _ptr(o), o.shape[1], mp, C.byref(self.out), self._stream())
         return self._obs()
 
     def step(self, action, end_mask=None):
@@ -336,7 +364,7 @@ class VecPlayEnv:
             return self._step_autoreset(a, end_mask)
         assert end_mask is None, 'end_mask needs VecPlayEnv(..., autoreset=True)'
         self._flip_pack()
-        _lib.check(self.lib, self.h, self.lib.rp_step(self.h, C.c_void_p(a.data_ptr()), C.byref(self.out), self._stream()), 'rp_step')
+        self._call('rp_step', _ptr(a), C.byref(self.out), self._stream())
         info = {'is_success': self.buf['is_success'], 'target_poses': self.buf['target_poses'], 'status': self.buf['status']}
         if self._done is None:      # environments.py:212: always False - one tensor for the handle's life (a fill kernel per step sat at the end of the step's chain: 8 us)
             self._done = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
@@ -347,12 +375,11 @@ class VecPlayEnv:
         if end_mask is not None:
             end_mask = end_mask.to(device=self.device, dtype=torch.uint8).contiguous()
             assert end_mask.shape == (self.num_envs,), end_mask.shape
-            mp = C.c_void_p(end_mask.data_ptr())
+            mp = _ptr(end_mask)
         self._flip_pack()
-        _lib.check(self.lib, self.h, self.lib.rp_step_autoreset(self.h, C.c_void_p(a.data_ptr()), mp, C.byref(self.out), C.byref(self.final_out),
-                                                                C.c_void_p(self._done_reason.data_ptr()), self._stream()), 'rp_step_autoreset')
+        self._call('rp_step_autoreset', _ptr(a), mp, C.byref(self.out), C.byref(self.final_out), _ptr(self._done_reason), self._stream())
         if self._table is not None:
-            _lib.check(self.lib, self.h, self.lib.rp_get_reset_rows(self.h, C.c_void_p(self._reset_row.data_ptr()), self._stream()), 'rp_get_reset_rows')
+            self._call('rp_get_reset_rows', _ptr(self._reset_row), self._stream())
         reason = self._done_reason
         info = {'is_success': self.buf['is_success'], 'target_poses': self.buf['target_poses'], 'status': self.buf['status'],
                 'terminal_observation': {k: self.final[k] for k in OBS_KEYS + ('gripper_proprioception',)},
@@ -371,14 +398,13 @@ class VecPlayEnv:
         if not self.autoreset:
             raise ValueError('set_reset_table needs VecPlayEnv(..., autoreset=True)')
         if o is None:
-            _lib.check(self.lib, self.h, self.lib.rp_set_reset_table(self.h, None, 0, 0, self._stream()), 'rp_set_reset_table')
+            self._call('rp_set_reset_table', None, 0, 0, self._stream())
             self._table = None
             self._reset_row.fill_(-1)
             return
         o = torch.as_tensor(o).to(device=self.device, dtype=torch.float32).contiguous()
         assert o.dim() == 2 and o.shape[0] > 0, o.shape
-        _lib.check(self.lib, self.h, self.lib.rp_set_reset_table(self.h, C.c_void_p(o.data_ptr()), o.shape[0], o.shape[1], self._stream()),
-                   'rp_set_reset_table')
+        self._call('rp_set_reset_table', _ptr(o), o.shape[0], o.shape[1], self._stream())
         self._table = o      # (kept until the next set: the copy reads it when the stream gets there)
 
     def random_start_table(self, m, seed):
@@ -401,7 +427,7 @@ class VecPlayEnv:
     def episode_steps(self):
         """int32 [N]: steps of every env's current episode (rp_step_autoreset counts them; reset() sets the reset envs' to 0)"""
         t = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib, self.h, self.lib.rp_get_episode_steps(self.h, C.c_void_p(t.data_ptr()), self._stream()), 'rp_get_episode_steps')
+        self._call('rp_get_episode_steps', _ptr(t), self._stream())
         return t
 
     @episode_steps.setter
@@ -409,76 +435,48 @@ class VecPlayEnv:
         """e.g. env.episode_steps = torch.arange(N) % limit: staggered time limits"""
         t = torch.as_tensor(steps).to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
         assert t.shape == (self.num_envs,), t.shape
-        _lib.check(self.lib, self.h, self.lib.rp_set_episode_steps(self.h, C.c_void_p(t.data_ptr()), self._stream()), 'rp_set_episode_steps')
-        self._ep_src = t      # (kept until the next set: the copy reads it when the stream gets there)
+        self._call('rp_set_episode_steps', _ptr(t), self._stream())
+        self._kept['rp_set_episode_steps'] = t      # (kept until the next set: the copy reads it when the stream gets there)
 
-    @property
-    def dynamics_names(self):
-        """{'friction': a name per collision object, 'mass': a name per free body}: the columns of get_dynamics / set_dynamics"""
-        return dynamics_names(MODEL_OF[self.env_id])
+    # ---- the per-env parameter tables and the state by column: every setter is _block per argument, _same_rows, _mask, one _call
+    def _dims_of(self, fn, n):
+        """the n int32 results of an rp_get_*_dims call: constants of the handle, so the library is asked once"""
+        dims = self._table_dims.get(fn)
+        if dims is None:
+            d = [C.c_int32() for _ in range(n)]
+            self._call(fn, *[C.byref(x) for x in d])
+            dims = self._table_dims[fn] = [x.value for x in d]
+        return dims
 
-    def get_dynamics(self):
-        """{'friction': [N, n_obj], 'mass': [N, n_free]} float32 device tensors: every env's lateral friction per collision object and mass per
-        free body (a fresh handle: the baked values)"""
-        no, nf = C.c_int32(), C.c_int32()
-        _lib.check(self.lib, self.h, self.lib.rp_get_dynamics_dims(self.h, C.byref(no), C.byref(nf)), 'rp_get_dynamics_dims')
-        fr = torch.empty((self.num_envs, no.value), dtype=torch.float32, device=self.device)
-        ms = torch.empty((self.num_envs, nf.value), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib, self.h, self.lib.rp_get_dynamics(self.h, C.c_void_p(fr.data_ptr()), C.c_void_p(ms.data_ptr()) if nf.value else None,
-                                                              self._stream()), 'rp_get_dynamics')
-        return {'friction': fr, 'mass': ms}
+    def _empty(self, *shape):
+        return torch.empty(shape, dtype=torch.float32, device=self.device)
 
-    def set_dynamics(self, friction=None, mass=None, mask=None):
-        """Per-env lateral friction per collision object ([N, n_obj] or [n_obj]: every env the same) and / or mass per free body ([N, n_free] or
-        [n_free]) for the envs where mask [N] != 0 (None: all); None leaves that parameter as it is.  A contact's friction is the product of its
-        objects' (at most 10); a body's inertia scales with its mass.  The values act from the next step or reset substep on this stream, and no
-        reset changes them.  Host values (numbers, numpy, CPU tensors) are checked (friction >= 0, mass > 0, finite); tensors on the env's device
-        are passed through without a host read, so the call can sit in a device-side loop (e.g. mask=done)."""
-        if friction is None and mass is None:
-            raise ValueError('set_dynamics: give friction, mass or both')
-        no, nf = C.c_int32(), C.c_int32()
-        _lib.check(self.lib, self.h, self.lib.rp_get_dynamics_dims(self.h, C.byref(no), C.byref(nf)), 'rp_get_dynamics_dims')
+    def _block(self, fn, what, v, shape, check, scalar=False):
+        """The argument `what` of `fn`, a value for a block of `shape` ((k,); (n_body, 6) for the wrench table; () for one joint) or for N of them, as (contiguous
+        float32 device tensor, rows = 1 or N); None gives (None, 0).  A tensor on the env's device goes through without a host read; any other value goes through
+        check (a check_*_values) and then to the device.  scalar: a host number stands for the whole block.  Another shape is a ValueError."""
+        if v is None:
+            return None, 0
         N = self.num_envs
+        on_dev = isinstance(v, torch.Tensor) and v.device == self.device
+        t = v.to(dtype=torch.float32) if on_dev else check(v).to(self.device)
+        if scalar and t.dim() == 0 and not on_dev:
+            t = t.expand(shape)
+        got = tuple(t.shape)
+        if got == shape:
+            return t.contiguous(), 1
+        if got == (N,) + shape:
+            return t.contiguous(), N
 
-        def prep(what, v, k):
-            if v is None:
-                return None, 0
-            on_dev = isinstance(v, torch.Tensor) and v.device == self.device
-            t = v.to(dtype=torch.float32) if on_dev else check_dynamics_values(what, v).to(self.device)
-            if t.dim() == 0 and not on_dev:
-                t = t.expand(k)
-            if t.dim() == 1 and t.shape[0] == k:
-                return t.contiguous(), 1
-            if t.dim() == 2 and t.shape == (N, k):
-                return t.contiguous(), N
-            raise ValueError('set_dynamics: %s has shape %s, expected [%d] or [%d, %d]' % (what, tuple(t.shape), k, N, k))
+        def text(sh):
+            return '[%s]' % ', '.join('%d' % n for n in sh)
+        raise ValueError('%s: %s has shape %s, expected %s or %s' % (fn, what, got, text(shape) if shape else 'a number', text((N,) + shape)))
 
-        fr, rf = prep('friction', friction, no.value)
-        ms, rm = prep('mass', mass, nf.value)
-        if fr is not None and ms is not None and rf != rm:      # one call, one row count: broadcast the single row
-            fr, ms = (fr.expand(N, -1).contiguous(), ms) if rf == 1 else (fr, ms.expand(N, -1).contiguous())
-        rows = rf or rm
-        mp = None
-        if mask is not None:
-            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous() if isinstance(mask, torch.Tensor) else \
-                torch.as_tensor(mask, dtype=torch.uint8).to(self.device)
-            if mask.shape != (N,):
-                raise ValueError('set_dynamics: mask has shape %s, expected [%d]' % (tuple(mask.shape), N))
-            mp = C.c_void_p(mask.data_ptr())
-        _lib.check(self.lib, self.h, self.lib.rp_set_dynamics(self.h, C.c_void_p(fr.data_ptr()) if fr is not None else None,
-                                                              C.c_void_p(ms.data_ptr()) if ms is not None and ms.numel() else None, rows, mp,
-                                                              self._stream()), 'rp_set_dynamics')
-        self._dyn_src = (fr, ms, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
-
-    @property
-    def wrench_names(self):
-        """a name per moving body: the body columns of get_wrench / set_wrench (arm links, free bodies, scene-joint bodies)"""
-        return wrench_names(MODEL_OF[self.env_id])
-
-    def _n_body(self):
-        na, nf, nj = C.c_int32(), C.c_int32(), C.c_int32()
-        _lib.check(self.lib, self.h, self.lib.rp_get_wrench_dims(self.h, C.byref(na), C.byref(nf), C.byref(nj)), 'rp_get_wrench_dims')
-        return na.value + nf.value + nj.value
+    def _same_rows(self, parts):
+        """the (tensor or None, rows) of one call's arguments -> ([tensor or None], rows): one call, one row count, so single rows are expanded to N when another
+        argument has N"""
+        rows = max(r for _, r in parts)
+        return [t.expand(self.num_envs, *t.shape).contiguous() if t is not None and r != rows else t for t, r in parts], rows
 
     def _mask(self, what, mask):
         if mask is None:
@@ -489,11 +487,47 @@ class VecPlayEnv:
             raise ValueError('%s: mask has shape %s, expected [%d]' % (what, tuple(mask.shape), self.num_envs))
         return mask
 
+    @property
+    def dynamics_names(self):
+        """{'friction': a name per collision object, 'mass': a name per free body}: the columns of get_dynamics / set_dynamics"""
+        return dynamics_names(MODEL_OF[self.env_id])
+
+    def get_dynamics(self):
+        """{'friction': [N, n_obj], 'mass': [N, n_free]} float32 device tensors: every env's lateral friction per collision object and mass per
+        free body (a fresh handle: the baked values)"""
+        no, nf = self._dims_of('rp_get_dynamics_dims', 2)
+        fr, ms = self._empty(self.num_envs, no), self._empty(self.num_envs, nf)
+        self._call('rp_get_dynamics', _ptr(fr), _ptr(ms) if nf else None, self._stream())
+        return {'friction': fr, 'mass': ms}
+
+    def set_dynamics(self, friction=None, mass=None, mask=None):
+        """Per-env lateral friction per collision object ([N, n_obj] or [n_obj]: every env the same) and / or mass per free body ([N, n_free] or
+        [n_free]) for the envs where mask [N] != 0 (None: all); None leaves that parameter as it is.  A contact's friction is the product of its
+        objects' (at most 10); a body's inertia scales with its mass.  The values act from the next step or reset substep on this stream, and no
+        reset changes them.  Host values (numbers, numpy, CPU tensors) are checked (friction >= 0, mass > 0, finite); tensors on the env's device
+        are passed through without a host read, so the call can sit in a device-side loop (e.g. mask=done)."""
+        if friction is None and mass is None:
+            raise ValueError('set_dynamics: give friction, mass or both')
+        widths = self._dims_of('rp_get_dynamics_dims', 2)
+        (fr, ms), rows = self._same_rows([self._block('set_dynamics', what, v, (k,), lambda x, what=what: check_dynamics_values(what, x), scalar=True)
+                                          for what, v, k in zip(('friction', 'mass'), (friction, mass), widths)])
+        mask = self._mask('set_dynamics', mask)
+        self._call('rp_set_dynamics', _ptr(fr), _ptr(ms) if ms is not None and ms.numel() else None, rows, _ptr(mask), self._stream())
+        self._kept['rp_set_dynamics'] = (fr, ms, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
+
+    @property
+    def wrench_names(self):
+        """a name per moving body: the body columns of get_wrench / set_wrench (arm links, free bodies, scene-joint bodies)"""
+        return wrench_names(MODEL_OF[self.env_id])
+
+    def _n_body(self):
+        return sum(self._dims_of('rp_get_wrench_dims', 3))
+
     def get_wrench(self):
         """[N, n_body, 6] float32 device tensor: every env's external force (through the centre of mass) and torque on each moving body, world
         coordinates, fx fy fz tx ty tz (a fresh handle: zeros)"""
-        w = torch.empty((self.num_envs, self._n_body(), 6), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib, self.h, self.lib.rp_get_wrench(self.h, C.c_void_p(w.data_ptr()), self._stream()), 'rp_get_wrench')
+        w = self._empty(self.num_envs, self._n_body(), 6)
+        self._call('rp_get_wrench', _ptr(w), self._stream())
         return w
 
     def set_wrench(self, wrench, mask=None):
@@ -501,22 +535,10 @@ class VecPlayEnv:
         wrench_names has them; per body a world force through its centre of mass and a world torque.  They act in every substep from the next step or
         reset substep on this stream until they are set again; no reset changes them.  Host values (sequences, numpy, CPU tensors) are checked finite;
         tensors on the env's device are passed through without a host read, so the call can sit in a device-side loop (set_wrench(None, mask=done))."""
-        N, nb = self.num_envs, self._n_body()
-        w, rows = None, 1
-        if wrench is not None:
-            on_dev = isinstance(wrench, torch.Tensor) and wrench.device == self.device
-            w = wrench.to(dtype=torch.float32) if on_dev else check_wrench_values(wrench).to(self.device)
-            if tuple(w.shape) == (nb, 6):
-                rows = 1
-            elif tuple(w.shape) == (N, nb, 6):
-                rows = N
-            else:
-                raise ValueError('set_wrench: wrench has shape %s, expected [%d, 6] or [%d, %d, 6]' % (tuple(w.shape), nb, N, nb))
-            w = w.contiguous()
+        w, rows = self._block('set_wrench', 'wrench', wrench, (self._n_body(), 6), check_wrench_values)
         mask = self._mask('set_wrench', mask)
-        _lib.check(self.lib, self.h, self.lib.rp_set_wrench(self.h, C.c_void_p(w.data_ptr()) if w is not None else None, rows,
-                                                            C.c_void_p(mask.data_ptr()) if mask is not None else None, self._stream()), 'rp_set_wrench')
-        self._wrench_src = (w, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
+        self._call('rp_set_wrench', _ptr(w), rows or 1, _ptr(mask), self._stream())
+        self._kept['rp_set_wrench'] = (w, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
 
     def push(self, body, force=None, torque=None, mask=None):
         """Set the force and / or the torque (3 values, or [N, 3]; None leaves that half as it is) on one body of wrench_names for the envs where
@@ -525,14 +547,9 @@ class VecPlayEnv:
             raise ValueError('push: give force, torque or both')
         b = self.wrench_names.index(body)
         w = self.get_wrench()
-        for half, v in ((0, force), (1, torque)):
-            if v is None:
-                continue
-            on_dev = isinstance(v, torch.Tensor) and v.device == self.device
-            t = v.to(dtype=torch.float32) if on_dev else check_wrench_values(v).to(self.device)
-            if tuple(t.shape) not in ((3,), (self.num_envs, 3)):
-                raise ValueError('push: %s has shape %s, expected [3] or [%d, 3]' % (('force', 'torque')[half], tuple(t.shape), self.num_envs))
-            w[:, b, 3 * half:3 * half + 3] = t
+        for half, what, v in ((0, 'force', force), (1, 'torque', torque)):
+            if v is not None:
+                w[:, b, 3 * half:3 * half + 3] = self._block('push', what, v, (3,), check_wrench_values)[0]
         self.set_wrench(w, mask=mask)
 
     @property
@@ -541,19 +558,14 @@ class VecPlayEnv:
         return actuation_names(MODEL_OF[self.env_id])
 
     def _n_arm(self):
-        na = C.c_int32()
-        _lib.check(self.lib, self.h, self.lib.rp_get_actuation_dims(self.h, C.byref(na)), 'rp_get_actuation_dims')
-        return na.value
+        return self._dims_of('rp_get_actuation_dims', 1)[0]
 
     def get_actuation(self):
         """{'gravity': [N, 3], 'motor_gain': [N, n_arm], 'motor_strength': [N, n_arm]} float32 device tensors: every env's gravity vector (m/s^2,
         world) and the gain and strength factor of each arm motor in dof order (a fresh handle: (0, 0, -9.8), ones, ones)"""
-        na = self._n_arm()
-        g = torch.empty((self.num_envs, 3), dtype=torch.float32, device=self.device)
-        kp = torch.empty((self.num_envs, na), dtype=torch.float32, device=self.device)
-        st = torch.empty((self.num_envs, na), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib, self.h, self.lib.rp_get_actuation(self.h, C.c_void_p(g.data_ptr()), C.c_void_p(kp.data_ptr()), C.c_void_p(st.data_ptr()),
-                                                               self._stream()), 'rp_get_actuation')
+        N, na = self.num_envs, self._n_arm()
+        g, kp, st = self._empty(N, 3), self._empty(N, na), self._empty(N, na)
+        self._call('rp_get_actuation', _ptr(g), _ptr(kp), _ptr(st), self._stream())
         return {'gravity': g, 'motor_gain': kp, 'motor_strength': st}
 
     def set_actuation(self, gravity=None, motor_gain=None, motor_strength=None, mask=None):
@@ -565,43 +577,24 @@ class VecPlayEnv:
         finite); tensors on the env's device are passed through without a host read, so the call can sit in a device-side loop (e.g. mask=done)."""
         if gravity is None and motor_gain is None and motor_strength is None:
             raise ValueError('set_actuation: give gravity, motor_gain, motor_strength or several')
-        N, na = self.num_envs, self._n_arm()
-
-        def prep(what, v, k):
-            if v is None:
-                return None, 0
-            on_dev = isinstance(v, torch.Tensor) and v.device == self.device
-            t = v.to(dtype=torch.float32) if on_dev else check_actuation_values(what, v).to(self.device)
-            if t.dim() == 1 and t.shape[0] == k:
-                return t.contiguous(), 1
-            if t.dim() == 2 and t.shape == (N, k):
-                return t.contiguous(), N
-            raise ValueError('set_actuation: %s has shape %s, expected [%d] or [%d, %d]' % (what, tuple(t.shape), k, N, k))
-
-        parts = [prep('gravity', gravity, 3), prep('motor_gain', motor_gain, na), prep('motor_strength', motor_strength, na)]
-        rows = max(r for _, r in parts)      # one call, one row count: single rows are broadcast when another part has N
-        parts = [t.expand(N, -1).contiguous() if t is not None and r != rows else t for t, r in parts]
+        na = self._n_arm()
+        parts, rows = self._same_rows([self._block('set_actuation', what, v, (k,), lambda x, what=what: check_actuation_values(what, x))
+                                       for what, v, k in (('gravity', gravity, 3), ('motor_gain', motor_gain, na), ('motor_strength', motor_strength, na))])
         mask = self._mask('set_actuation', mask)
-        _lib.check(self.lib, self.h, self.lib.rp_set_actuation(self.h, *[C.c_void_p(t.data_ptr()) if t is not None else None for t in parts], rows,
-                                                               C.c_void_p(mask.data_ptr()) if mask is not None else None, self._stream()),
-                   'rp_set_actuation')
-        self._act_src = (parts, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
+        self._call('rp_set_actuation', *[_ptr(t) for t in parts], rows, _ptr(mask), self._stream())
+        self._kept['rp_set_actuation'] = (parts, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
 
     @property
     def kinematics_names(self):
         """{'pos': a name per column of get_kinematics()['pos'], 'vel': of ['vel']}: arm dofs, free bodies' pose / velocity components, scene joints"""
-        names = getattr(self, '_kin_names', None)
-        if names is None:          # (read from the bake once per handle: set_body / set_joint look columns up in every call)
-            names = self._kin_names = kinematics_names(MODEL_OF[self.env_id])
-        return dict(names)
+        return kinematics_names(MODEL_OF[self.env_id])
 
     def get_kinematics(self):
         """{'pos': [N, n_pos], 'vel': [N, n_vel]} float32 device tensors: every env's joint positions, free-body poses (x y z qx qy qz qw) and scene-joint
         positions, and the matching velocities (free bodies: world linear and angular), columns as kinematics_names has them"""
         names = self.kinematics_names
-        p = torch.empty((self.num_envs, len(names['pos'])), dtype=torch.float32, device=self.device)
-        v = torch.empty((self.num_envs, len(names['vel'])), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib, self.h, self.lib.rp_get_kinematics(self.h, C.c_void_p(p.data_ptr()), C.c_void_p(v.data_ptr()), self._stream()), 'rp_get_kinematics')
+        p, v = self._empty(self.num_envs, len(names['pos'])), self._empty(self.num_envs, len(names['vel']))
+        self._call('rp_get_kinematics', _ptr(p), _ptr(v), self._stream())
         return {'pos': p, 'vel': v}
 
     def set_kinematics(self, pos=None, vel=None, mask=None, clear_contacts=False):
@@ -612,36 +605,12 @@ class VecPlayEnv:
         are passed through without a host read, so the call can sit in a device-side loop (e.g. mask=done)."""
         if pos is None and vel is None:
             raise ValueError('set_kinematics: give pos, vel or both')
-        N, names = self.num_envs, self.kinematics_names
-
-        def prep(what, v):
-            if v is None:
-                return None, 0
-            k = len(names[what])
-            on_dev = isinstance(v, torch.Tensor) and v.device == self.device
-            t = v.to(dtype=torch.float32) if on_dev else check_kinematics_values(what, v, names[what]).to(self.device)
-            if t.dim() == 1 and t.shape[0] == k:
-                return t.contiguous(), 1
-            if t.dim() == 2 and t.shape == (N, k):
-                return t.contiguous(), N
-            raise ValueError('set_kinematics: %s has shape %s, expected [%d] or [%d, %d]' % (what, tuple(t.shape), k, N, k))
-
-        parts = [prep('pos', pos), prep('vel', vel)]
-        rows = max(r for _, r in parts)      # one call, one row count: a single row is broadcast when the other half has N
-        parts = [t.expand(N, -1).contiguous() if t is not None and r != rows else t for t, r in parts]
+        names = self.kinematics_names
+        parts, rows = self._same_rows([self._block('set_kinematics', what, v, (len(names[what]),), lambda x, what=what: check_kinematics_values(what, x, names[what]))
+                                       for what, v in (('pos', pos), ('vel', vel))])
         mask = self._mask('set_kinematics', mask)
-        _lib.check(self.lib, self.h, self.lib.rp_set_kinematics(self.h, *[C.c_void_p(t.data_ptr()) if t is not None else None for t in parts], rows,
-                                                                C.c_void_p(mask.data_ptr()) if mask is not None else None,
-                                                                _lib.KIN_CLEAR_CONTACTS if clear_contacts else 0, self._stream()), 'rp_set_kinematics')
-        self._kin_src = (parts, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
-
-    def _columns(self, what, t, names, cols, v):
-        """t[:, cols] = v ([len(cols)] or [N, len(cols)]; a device tensor as it is, host values checked as columns `names`)"""
-        on_dev = isinstance(v, torch.Tensor) and v.device == self.device
-        x = v.to(dtype=torch.float32) if on_dev else check_kinematics_values(what, v, names).to(self.device)
-        if tuple(x.shape) not in ((len(names),), (self.num_envs, len(names))):
-            raise ValueError('%s has shape %s, expected [%d] or [%d, %d]' % (what, tuple(x.shape), len(names), self.num_envs, len(names)))
-        t[:, cols[0]:cols[0] + len(cols)] = x
+        self._call('rp_set_kinematics', *[_ptr(t) for t in parts], rows, _ptr(mask), _lib.KIN_CLEAR_CONTACTS if clear_contacts else 0, self._stream())
+        self._kept['rp_set_kinematics'] = (parts, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
 
     def set_body(self, name, pos=None, quat=None, lin_vel=None, ang_vel=None, mask=None, clear_contacts=False):
         """Place one free body of wrench_names ('block', 'drawer', ...): position (3 values or [N, 3]), orientation quaternion (xyzw, 4 or [N, 4]), world linear
@@ -656,7 +625,8 @@ class VecPlayEnv:
         kin = self.get_kinematics()
         for what, tab, v, c0, k in (('pos', 'pos', pos, p0, 3), ('quat', 'pos', quat, p0 + 3, 4), ('lin_vel', 'vel', lin_vel, v0, 3), ('ang_vel', 'vel', ang_vel, v0 + 3, 3)):
             if v is not None:
-                self._columns('set_body: ' + what, kin[tab], names[tab][c0:c0 + k], range(c0, c0 + k), v)
+                cols = names[tab][c0:c0 + k]
+                kin[tab][:, c0:c0 + k] = self._block('set_body', what, v, (k,), lambda x: check_kinematics_values('set_body: ' + what, x, cols))[0]
         self.set_kinematics(pos=kin['pos'] if pos is not None or quat is not None else None,
                             vel=kin['vel'] if lin_vel is not None or ang_vel is not None else None, mask=mask, clear_contacts=clear_contacts)
 
@@ -670,14 +640,14 @@ class VecPlayEnv:
         if name not in names['pos'] or '.' in name:
             raise KeyError('set_joint: %r is neither a dof nor a scene joint of %s' % (name, self.env_id))
         kin = self.get_kinematics()
+
+        def number(what, x):      # (this call looks at a host value's shape before its entries: a wrongly shaped one goes to _block unchecked, which refuses it)
+            t = torch.as_tensor(x, dtype=torch.float32, device='cpu')
+            return _check_values('set_joint: ' + what, t) if tuple(t.shape) in ((), (self.num_envs,)) else t
+
         for what, tab, v in (('q', 'pos', q), ('qd', 'vel', qd)):
             if v is not None:
-                on_dev = isinstance(v, torch.Tensor) and v.device == self.device
-                x = v if on_dev else torch.as_tensor(v, dtype=torch.float32, device='cpu')
-                if tuple(x.shape) not in ((), (self.num_envs,)):
-                    raise ValueError('set_joint: %s has shape %s, expected a number or [%d]' % (what, tuple(x.shape), self.num_envs))
-                c = names[tab].index(name)
-                self._columns('set_joint: ' + what, kin[tab], (name,), (c,), x[..., None])
+                kin[tab][:, names[tab].index(name)] = self._block('set_joint', what, v, (), functools.partial(number, what))[0]
         self.set_kinematics(pos=kin['pos'] if q is not None else None, vel=kin['vel'] if qd is not None else None, mask=mask)
 
     def clone_envs(self, src, mask=None, episode_steps=True):
@@ -701,13 +671,12 @@ class VecPlayEnv:
             raise ValueError('clone_envs: src has shape %s, expected [%d]' % (tuple(t.shape), N))
         t = t.contiguous()
         mask = self._mask('clone_envs', mask)
-        _lib.check(self.lib, self.h, self.lib.rp_copy_envs(self.h, C.c_void_p(t.data_ptr()), C.c_void_p(mask.data_ptr()) if mask is not None else None,
-                                                           _lib.COPY_EPISODE_STEPS if episode_steps else 0, self._stream()), 'rp_copy_envs')
-        self._clone_src = (t, mask)      # (kept until the next call: the kernel reads them when the stream gets there)
+        self._call('rp_copy_envs', _ptr(t), _ptr(mask), _lib.COPY_EPISODE_STEPS if episode_steps else 0, self._stream())
+        self._kept['rp_copy_envs'] = (t, mask)      # (kept until the next call: the kernel reads them when the stream gets there)
 
     def calc_state(self):
         self._flip_pack()
-        _lib.check(self.lib, self.h, self.lib.rp_calc_state(self.h, C.byref(self.out), self._stream()), 'rp_calc_state')
+        self._call('rp_calc_state', C.byref(self.out), self._stream())
         return self._obs()
 
     def reset_goal_pos(self, goal=None, mask=None):
@@ -715,11 +684,11 @@ class VecPlayEnv:
         if goal is not None:
             goal = goal.to(device=self.device, dtype=torch.float32).contiguous()
             assert goal.shape == (self.num_envs, self.dims['desired_goal'])
-            gp = C.c_void_p(goal.data_ptr())
+            gp = _ptr(goal)
         if mask is not None:
             mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mp = C.c_void_p(mask.data_ptr())
-        _lib.check(self.lib, self.h, self.lib.rp_reset_goal(self.h, gp, mp, self._stream()), 'rp_reset_goal')
+            mp = _ptr(mask)
+        self._call('rp_reset_goal', gp, mp, self._stream())
 
     def compute_reward_sparse(self, achieved_goal, desired_goal, info=None):
         """the sparse formula (environments.py:278-304) whatever `sparse` the env was built with"""
@@ -731,8 +700,7 @@ class VecPlayEnv:
         w = self.dims['achieved_goal']
         ag2, dg2 = ag.reshape(-1, w), dg.reshape(-1, w)
         r = torch.empty(ag2.shape[0], dtype=torch.float32, device=self.device)
-        _lib.check(self.lib, self.h, getattr(self.lib, _fn)(self.h, C.c_void_p(ag2.data_ptr()), C.c_void_p(dg2.data_ptr()),
-                                                             C.c_void_p(r.data_ptr()), ag2.shape[0], self._stream()), _fn)
+        self._call(_fn, _ptr(ag2), _ptr(dg2), _ptr(r), ag2.shape[0], self._stream())
         return r.reshape(ag.shape[:-1])
 
     @property
@@ -766,15 +734,13 @@ class VecPlayEnv:
         if sub_goal is not None:
             sub_goal = sub_goal.to(device=self.device, dtype=torch.float32).contiguous()
             assert sub_goal.shape == (n, self.dims['achieved_goal']), sub_goal.shape
-            sg = C.c_void_p(sub_goal.data_ptr())
+            sg = _ptr(sub_goal)
         if ghost_arm is not None:
             ghost_arm = ghost_arm.to(device=self.device, dtype=torch.float32).contiguous()
             assert ghost_arm.shape == (n, 8), ghost_arm.shape
-            _lib.check(self.lib, self.h, self.lib.rp_render_ex(self.h, C.byref(camera) if camera is not None else None, int(width), int(height), lo, n,
-                                                               C.c_void_p(img.data_ptr()), sg, C.c_void_p(ghost_arm.data_ptr()), self._stream()), 'rp_render_ex')
+            self._call('rp_render_ex', C.byref(camera) if camera is not None else None, int(width), int(height), lo, n, _ptr(img), sg, _ptr(ghost_arm), self._stream())
             return img
-        _lib.check(self.lib, self.h, self.lib.rp_render(self.h, C.byref(camera) if camera is not None else None, int(width), int(height), lo, n,
-                                                        C.c_void_p(img.data_ptr()), sg, self._stream()), 'rp_render')
+        self._call('rp_render', C.byref(camera) if camera is not None else None, int(width), int(height), lo, n, _ptr(img), sg, self._stream())
         return img
 
     def ray_test(self, ray_from, ray_to):
@@ -789,16 +755,14 @@ class VecPlayEnv:
                'link': torch.empty((self.num_envs, k), dtype=torch.int32, device=self.device),
                'hit_position': torch.empty((self.num_envs, k, 3), dtype=torch.float32, device=self.device),
                'hit_normal': torch.empty((self.num_envs, k, 3), dtype=torch.float32, device=self.device)}
-        _lib.check(self.lib, self.h, self.lib.rp_ray_test(self.h, C.c_void_p(f.data_ptr()), C.c_void_p(t.data_ptr()), k, C.c_void_p(out['hit_fraction'].data_ptr()),
-                                                          C.c_void_p(out['collider'].data_ptr()), C.c_void_p(out['link'].data_ptr()),
-                                                          C.c_void_p(out['hit_position'].data_ptr()), C.c_void_p(out['hit_normal'].data_ptr()), self._stream()),
-                   'rp_ray_test')
+        self._call('rp_ray_test', _ptr(f), _ptr(t), k, _ptr(out['hit_fraction']), _ptr(out['collider']), _ptr(out['link']), _ptr(out['hit_position']),
+                   _ptr(out['hit_normal']), self._stream())
         return out
 
     def get_state(self):
         n = self.lib.rp_state_bytes(self.h) // 4
         s = torch.empty((self.num_envs, n), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib, self.h, self.lib.rp_get_state(self.h, C.c_void_p(s.data_ptr()), self._stream()), 'rp_get_state')
+        self._call('rp_get_state', _ptr(s), self._stream())
         return s
 
     def set_state(self, s):
@@ -811,7 +775,7 @@ class VecPlayEnv:
         if s.shape[1] < n:
             s = torch.cat([s, torch.zeros((s.shape[0], n - s.shape[1]), dtype=torch.float32, device=self.device)], 1)
         s = s.contiguous()
-        _lib.check(self.lib, self.h, self.lib.rp_set_state(self.h, C.c_void_p(s.data_ptr()), s.shape[0], self._stream()), 'rp_set_state')
+        self._call('rp_set_state', _ptr(s), s.shape[0], self._stream())
 
     def replay(self, o0, actions, keys=('obs_quat', 'achieved_goal')):
         """Play recorded trajectories back (the reference's README use: "playing out the teleop data", "reset the environment to
@@ -835,31 +799,31 @@ class VecPlayEnv:
     def set_fused(self, mode=1):
         """step pipeline: 0 = default (k_action, k_prep2, k_solve2, k_calc_state), 1 = one fused kernel per step (the
         library's in-GPU cross-check path).  Both are bit-identical."""
-        _lib.check(self.lib, self.h, self.lib.rp_set_fused(self.h, int(mode)), 'rp_set_fused')
+        self._call('rp_set_fused', int(mode))
 
     def set_groups(self, groups):
         """number of env groups (each with its own stream and kernel chain) rp_step uses; results do not depend on it"""
-        _lib.check(self.lib, self.h, self.lib.rp_set_groups(self.h, int(groups)), 'rp_set_groups')
+        self._call('rp_set_groups', int(groups))
 
     def set_debug_flags(self, flags):
         """test hook: bit 0 makes the solver give every contact its own folded slot (its fallback layout) instead of solving
         arm-only and non-arm contacts side by side; results are bit-identical either way"""
-        _lib.check(self.lib, self.h, self.lib.rp_set_debug_flags(self.h, int(flags)), 'rp_set_debug_flags')
+        self._call('rp_set_debug_flags', int(flags))
 
     def debug_row_counts(self):
         """test hook: per env of the latest substep, [unit rows, contacts, 1 if an arm contact, spanning contacts] (host tensor)"""
         buf = (C.c_int32 * (2 * self.num_envs))()
-        _lib.check(self.lib, self.h, self.lib.rp_debug_row_counts(self.h, buf), 'rp_debug_row_counts')
+        self._call('rp_debug_row_counts', buf)
         a = torch.tensor(list(buf), dtype=torch.int64).reshape(self.num_envs, 2)
         return torch.stack([a[:, 0], a[:, 1] % 1000, (a[:, 1] // 1000) % 100, a[:, 1] // 100000], 1)
 
     def enable_timers(self, steps=64):
         """keep per-launch hipEvent timings for the next `steps` rp_step calls (0 disables)"""
-        _lib.check(self.lib, self.h, self.lib.rp_enable_timers(self.h, int(steps)), 'rp_enable_timers')
+        self._call('rp_enable_timers', int(steps))
 
     def timers(self):
         t = _lib.RpTimers()
-        _lib.check(self.lib, self.h, self.lib.rp_get_timers(self.h, C.byref(t)), 'rp_get_timers')
+        self._call('rp_get_timers', C.byref(t))
         return {n: getattr(t, n) for n, _ in _lib.RpTimers._fields_}
 
     def debug_action(self, actions, places=False):
@@ -871,11 +835,11 @@ class VecPlayEnv:
         assert a.shape == (self.num_envs, self.dims['action']), a.shape
         raw = torch.empty((self.num_envs, 8), dtype=torch.float32, device=self.device)
         torch.cuda.current_stream(self.device).synchronize()      # (the hook runs on the NULL stream)
-        _lib.check(self.lib, self.h, self.lib.rp_debug_action(self.h, C.c_void_p(a.data_ptr()), C.c_void_p(raw.data_ptr())), 'rp_debug_action')
+        self._call('rp_debug_action', _ptr(a), _ptr(raw))
         word = raw[:, 7].to(torch.int32)
         return (raw[:, :7].contiguous(), word & 3) + ((word >> 2,) if places else ())
 
     def debug_substep(self, env=0):
         buf = (C.c_float * 4096)()
-        _lib.check(self.lib, self.h, self.lib.rp_debug_substep(self.h, env, buf), 'rp_debug_substep')
+        self._call('rp_debug_substep', env, buf)
         return torch.tensor(list(buf))

@@ -1,17 +1,11 @@
 """rp_step_autoreset's C ABI (0.5) on a GPU-less host: declared in include/rp_playroom.h, exported by both libraries, mirrored in _lib and in VecPlayEnv."""
 import ctypes
 import inspect
-import os
 import re
-import subprocess
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_decl import assert_exported_by_both_libraries, header as _header
+
 NEW = ('rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset')
-
-
-def _header():
-    src = open(os.path.join(REPO, 'include', 'rp_playroom.h')).read()
-    return re.sub(r'/\*.*?\*/', '', src, flags=re.S)
 
 
 def test_new_entry_points_are_declared():
@@ -25,17 +19,11 @@ def test_new_entry_points_are_declared():
 
 def test_new_entry_points_are_exported_by_both_libraries_and_mirrored():
     from roboticsplayroompybullet_amd import _lib
-    _lib.build()
+    assert_exported_by_both_libraries(NEW)
     for path in (_lib.LIB_PATH, _lib.WIDE_LIB_PATH):
-        out = subprocess.run(['nm', '-D', '--defined-only', path], check=True, capture_output=True, text=True).stdout
-        exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == 'T'}
-        for name in NEW:
-            assert name in exported, (name, path)
         lib = ctypes.CDLL(path)
         lib.rp_version.restype = ctypes.c_char_p
         assert b'rp_playroom 0.5' in lib.rp_version()
-    for name in NEW:
-        assert name in _lib.EXPORTS, name
     for wide in (False, True):
         lib = _lib.load(wide=wide)
         assert len(lib.rp_step_autoreset.argtypes) == 7

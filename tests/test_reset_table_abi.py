@@ -2,23 +2,11 @@
 VecPlayEnv, their kernels compiled into both code objects; and the row rule (tests/reset_rows.py) on hand-worked cases."""
 import ctypes
 import inspect
-import os
-import re
-import subprocess
 
+from abi_decl import assert_exported_by_both_libraries, decl as _decl, header as _header
 from reset_rows import reset_rows
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('rp_set_reset_table', 'rp_get_reset_rows')
-
-
-def _header():
-    src = open(os.path.join(REPO, 'include', 'rp_playroom.h')).read()
-    return re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-
-
-def _decl(src, name):
-    return ' '.join(re.search(r'int %s\((.*?)\);' % name, src, flags=re.S).group(1).replace(',', ' , ').split())
 
 
 def test_entry_points_are_declared():
@@ -29,14 +17,7 @@ def test_entry_points_are_declared():
 
 def test_entry_points_are_exported_by_both_libraries_and_mirrored():
     from roboticsplayroompybullet_amd import _lib
-    _lib.build()
-    for path in (_lib.LIB_PATH, _lib.WIDE_LIB_PATH):
-        out = subprocess.run(['nm', '-D', '--defined-only', path], check=True, capture_output=True, text=True).stdout
-        exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == 'T'}
-        for name in NEW:
-            assert name in exported, (name, path)
-    for name in NEW:
-        assert name in _lib.EXPORTS, name
+    assert_exported_by_both_libraries(NEW)
     vp = ctypes.c_void_p
     for wide in (False, True):
         lib = _lib.load(wide=wide)
