@@ -238,6 +238,28 @@ int rp_render(rp_handle h, const rp_camera* cam, int32_t width, int32_t height, 
  * default IK call from the rest pose finds for that pose (ENV:575-590).  Panda models only: RP_ERR_UNSUPPORTED for a UR5 (the reference raises NotImplementedError). */
 int rp_render_ex(rp_handle h, const rp_camera* cam, int32_t width, int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb,
                  const float* sub_goal, const float* ghost_arm, void* stream);
+/* all three layers of getCameraImage (ENV:841-845 takes [2], the colour) for envs [first_env, first_env + num_envs), row 0 = top; each output may be NULL, not all three:
+ *   rgb [num_envs, height, width, 3] uint8: byte for byte what rp_render_ex writes for the same arguments (ghosts blended at 0.5, same background, rays 0 .. 10 m).
+ *   depth [num_envs, height, width] float: the nearest NON-ghost hit of the pixel's ray as eye-space z = t (d . forward), d the normalised ray direction, t the hit
+ *     parameter (on a sphere evaluated through the point of closest approach, which does not cancel at a grazing ray as rp_ray_test's float32 quadratic does: the two
+ *     differ there by up to some 1e-4 m, elsewhere by rounding).  RP_DEPTH_BUFFER: PyBullet's depthBuffer value far (z - near) / (z (far - near)) clamped to [0, 1]; exactly 1.0 on a miss.  RP_DEPTH_METRES: z itself;
+ *     exactly far_plane on a miss.  near_plane / far_plane only shape this value; they do not clip rays (as for rp_camera above).
+ *   segmentation [num_envs, height, width] int32: -1 on a miss, else collider | ((link + 1) << 24) with the collider and link rp_ray_test reports for that ray
+ *     (PyBullet's packing, the collider index standing where the body's unique id stands).
+ * Ghosts (sub_goal, ghost_arm: as for rp_render_ex) are see-through markers: they tint rgb and never appear in depth or segmentation, as rp_ray_test ignores them.
+ * Cameras: cam as for rp_render (NULL = rp_default_camera; the gripper camera, mode 1, is per env already), OR cam_rows, a DEVICE array [num_envs, 11], row i for env
+ * first_env + i: eye[3] target[3] up[3] fov_deg aspect, from which the kernel builds the basis rp_render builds on the host from an rp_camera (same operations, in
+ * double, zero-length vectors included).  Never both.  The library does not range-check device values (fov in (0, 180), aspect > 0 are the caller's to keep).
+ * RP_ERR_ARG: all three outputs NULL, both cam and cam_rows, near_plane <= 0, far_plane <= near_plane, an unknown depth mode, rp_render_ex's size and range errors.
+ * RP_ERR_UNSUPPORTED: a ghost arm on a UR5.  Enqueued on `stream`: no host wait, no host read of device values. */
+enum rp_depth_mode { RP_DEPTH_BUFFER = 0, RP_DEPTH_METRES = 1 };
+int rp_render_layers(rp_handle h, const rp_camera* cam, const float* cam_rows /* device [num_envs, 11] or NULL */,
+                     float near_plane, float far_plane, int32_t depth_mode,
+                     int32_t width, int32_t height, int32_t first_env, int32_t num_envs,
+                     uint8_t* rgb /* [num_envs, height, width, 3] or NULL */,
+                     float* depth /* [num_envs, height, width] or NULL */,
+                     int32_t* segmentation /* [num_envs, height, width] or NULL */,
+                     const float* sub_goal, const float* ghost_arm, void* stream);
 /* bullet_client.rayTest(from, to) (ENV:738-741) for k rays per env: from / to [N, k, 3] world coordinates.  Outputs (each may be NULL):
  * hit_fraction [N, k] (1 on a miss), collider [N, k] (index into the model's collider table, -1 on a miss), link [N, k] (Bullet link
  * index of an arm collider, -1 otherwise), hit_position [N, k, 3], hit_normal [N, k, 3].  A ray that starts inside a shape does not hit it. */

@@ -51,6 +51,8 @@ DONE_TIME_LIMIT, DONE_END_MASK, DONE_FAULT, DONE_SUCCESS = 1, 2, 4, 8
 # rp_kin_flags / rp_copy_flags (include/rp_playroom.h)
 KIN_CLEAR_CONTACTS = 1
 COPY_EPISODE_STEPS = 1
+# rp_depth_mode (include/rp_playroom.h)
+DEPTH_BUFFER, DEPTH_METRES = 0, 1
 ACTION_TYPE_CODES = {'absolute_rpy': 0, 'relative_rpy': 1, 'absolute_quat': 2, 'relative_quat': 3, 'absolute_joints': 4, 'relative_joints': 5}
 
 
@@ -80,13 +82,13 @@ class RpTimers(C.Structure):
 
 EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 'rp_reset_goal', 'rp_step', 'rp_calc_state',
            'rp_compute_reward', 'rp_compute_reward_sparse', 'rp_state_bytes', 'rp_get_state', 'rp_set_state', 'rp_get_timers', 'rp_enable_timers',
-           'rp_last_error', 'rp_version', 'rp_default_camera', 'rp_camera_from_yaw_pitch_roll', 'rp_render', 'rp_render_ex', 'rp_ray_test',
+           'rp_last_error', 'rp_version', 'rp_default_camera', 'rp_camera_from_yaw_pitch_roll', 'rp_render', 'rp_render_ex', 'rp_render_layers', 'rp_ray_test',
            'rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset', 'rp_set_reset_table', 'rp_get_reset_rows',
            'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench',
            'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
-                 'rp_debug_autoreset_shape', 'rp_debug_action']
+                 'rp_debug_autoreset_shape', 'rp_debug_action', 'rp_debug_render_cull']
 
 _lib = None
 _libs = {}
@@ -151,6 +153,7 @@ def load(wide=False):
     lib.rp_camera_from_yaw_pitch_roll.argtypes = [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(RpCamera)]
     lib.rp_render.argtypes = [vp, C.POINTER(RpCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
     lib.rp_render_ex.argtypes = [vp, C.POINTER(RpCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+    lib.rp_render_layers.argtypes = [vp, C.POINTER(RpCamera), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_ray_test.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_debug_substep.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
     lib.rp_set_fused.argtypes = [vp, C.c_int32]
@@ -161,6 +164,7 @@ def load(wide=False):
     lib.rp_debug_reset_rounds.argtypes = [vp]
     lib.rp_debug_autoreset_shape.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.rp_debug_action.argtypes = [vp, vp, vp]
+    lib.rp_debug_render_cull.argtypes = [vp, C.c_int32]
     _libs[path] = lib
     if not wide:
         _lib = lib

@@ -10,6 +10,7 @@
  *
  *   k_collider_poses   one wave per env: FK -> world pose, half extents, colour of every collider (+ the ghosts of a sub-goal)
  *   k_render           256 pixels per block, the env's collider table staged in LDS, nearest hit per pixel
+ *   k_render_layers    a 16 x 16 pixel tile per block, the tile's shortlist of records in LDS: colour, depth and segmentation; per-env cameras (rp_render_layers)
  *   k_ray_test         K rays per env against the same table: hit fraction, position, normal, collider, Bullet link index */
 #pragma once
 
@@ -226,6 +227,145 @@ __global__ void __launch_bounds__(256) k_render(const DevModel* __restrict__ m, 
   o[0] = (unsigned char)(fminf(fmaxf(colr.x, 0.f), 1.f) * 255.f + 0.5f);
   o[1] = (unsigned char)(fminf(fmaxf(colr.y, 0.f), 1.f) * 255.f + 0.5f);
   o[2] = (unsigned char)(fminf(fmaxf(colr.z, 0.f), 1.f) * 255.f + 0.5f);
+}
+
+/* rp_render_layers: colour, depth and segmentation of getCameraImage in one pass, a 16 x 16 pixel tile per block.
+ *
+ * The block first builds its view (thread 0: the camera's basis - from the launch's RpCamera, from the EE pose for the gripper camera, or from the env's row of
+ * cam_rows with device_camera's operations in double) and then the tile's SHORTLIST: one lane per collider record tests the record's bounding sphere (centre p, radius |he|
+ * for a box or the box around a hull, r for a sphere) against the four side planes of the tile's frustum - the pyramid with the eye as apex through the centres of the
+ * tile's outermost pixels, whose nx / ny are computed by the very expression the pixels use, so every pixel-centre ray of the tile lies inside it.  A record is dropped only
+ * when its sphere lies wholly outside one of the planes by more than a pad of 1e-3 of the distances involved (fp32 rounds at 6e-8; the basis is orthonormal to about 1e-6):
+ * then no pixel-centre ray of the tile can meet it, and dropping it cannot change a pixel.  Ballots and a prefix count over the four waves compact the survivors into LDS in
+ * ASCENDING record order, so that the lowest record still wins a tie as in k_render.  Each pixel then walks the shortlist with k_render's ray, hit tests and shading
+ * (-ffp-contract=off: equal expressions, equal bits).  cull == 0 (rp_debug_render_cull): every record is on every tile's list.
+ *
+ * depth: the nearest NON-ghost hit as eye-space z = t (d . fwd) - t the hit parameter of the winning record, for a sphere re-evaluated in a well-conditioned form (below; which
+ * record wins, and the colour, stay with rc_ray_sphere's t) -; RP_DEPTH_BUFFER far (z - near) / (z (far - near)) clamped to [0, 1], 1 on a miss; RP_DEPTH_METRES z, far on
+ * a miss.  seg: collider | (link + 1) << 24 of that hit (rp_ray_test's collider and link), -1 on a miss.  Ghosts tint rgb only. */
+static_assert(RC_MAX <= 256, "k_render_layers: one lane per record");
+__global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, int num, RpCamera cam,
+                                                       const float* __restrict__ cam_rows, const float* __restrict__ ee_pose, int width, int height, int cull,
+                                                       float near_plane, float far_plane, int metres, unsigned char* __restrict__ rgb, float* __restrict__ depth,
+                                                       int* __restrict__ seg) {
+  __shared__ float T[RC_MAX * RC_STRIDE];      /* the shortlist's records, compacted */
+  __shared__ float V[14];                      /* eye, fwd, right, up, tan_half_fov, aspect */
+  __shared__ int list[RC_MAX];
+  __shared__ int wcnt[4];
+  const int tiles_x = (width + 15) >> 4, tiles = tiles_x * ((height + 15) >> 4);
+  /* tile-major: consecutive blocks are the SAME tile of consecutive envs.  Blocks go to the eight XCDs round robin; env-major, with a tile count that is a multiple of
+   * eight (64 x 64: 16), the few tiles that hold the arm - whose hulls cost a ray hundreds of plane tests - would always land on the same XCDs */
+  const int tile = blockIdx.x / num, slot = blockIdx.x - tile * num;
+  if (tile >= tiles) return;
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) {
+    if (cam_rows) {      /* device_camera (rp_playroom.hip), operation by operation */
+      const float* c = cam_rows + 11 * (size_t)slot;
+      double f[3], u[3], s[3], nn = 0;
+      for (int k = 0; k < 3; k++) { f[k] = c[3 + k] - c[k]; nn += f[k] * f[k]; }
+      nn = sqrt(nn > 0 ? nn : 1);
+      for (int k = 0; k < 3; k++) f[k] /= nn;
+      s[0] = f[1] * c[8] - f[2] * c[7]; s[1] = f[2] * c[6] - f[0] * c[8]; s[2] = f[0] * c[7] - f[1] * c[6];
+      nn = sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]); nn = nn > 0 ? nn : 1;
+      for (int k = 0; k < 3; k++) s[k] /= nn;
+      u[0] = s[1] * f[2] - s[2] * f[1]; u[1] = s[2] * f[0] - s[0] * f[2]; u[2] = s[0] * f[1] - s[1] * f[0];
+      for (int k = 0; k < 3; k++) { V[k] = c[k]; V[3 + k] = (float)f[k]; V[6 + k] = (float)s[k]; V[9 + k] = (float)u[k]; }
+      V[12] = (float)tan(0.5 * c[9] * 0.01745329251994329547); V[13] = c[10];
+    } else {
+      V3 eye = ld3(cam.eye), fwd = ld3(cam.fwd), right = ld3(cam.right), up = ld3(cam.up);
+      if (cam.mode == 1) {       /* gripper_camera, as in k_render */
+        const float* e = ee_pose + 12 * slot;
+        const M3 R = ldm3(e + 3);
+        eye = ld3(e);
+        fwd = col(R, 2) * -1.f; up = col(R, 0); right = cross(fwd, up);
+      }
+      st3(V, eye); st3(V + 3, fwd); st3(V + 6, right); st3(V + 9, up);
+      V[12] = cam.tan_half_fov; V[13] = cam.aspect;
+    }
+  }
+  __syncthreads();
+  const V3 eye = ld3(V), fwd = ld3(V + 3), right = ld3(V + 6), up = ld3(V + 9);
+  const float thf = V[12], aspect = V[13];
+  const int n = min(cnt[slot], RC_MAX);
+  const float* G = tab + (size_t)slot * RC_MAX * RC_STRIDE;
+  bool keep = tid < n;
+  if (keep && cull) {
+    const float* rec = G + tid * RC_STRIDE;
+    const V3 q = ld3(rec + 9) - eye, he = ld3(rec + 12);
+    const int tw = __float_as_int(rec[18]);
+    const float r = (!(tw & RC_HULL) && (tw & 0xFF) != 0) ? he.x : norm(he);      /* a sphere's radius; the corner of a box or of the box around a hull */
+    const float qx = dot(q, right), qy = dot(q, up), qz = dot(q, fwd);
+    const float pad = r + 1e-3f * (r + fabsf(qx) + fabsf(qy) + fabsf(qz)) + 1e-4f;
+    const int x1 = min(16 * tx + 15, width - 1), y1 = min(16 * ty + 15, height - 1);
+    const float nxa = (2.f * (16 * tx + 0.5f) / width - 1.f) * thf * aspect, nxb = (2.f * (x1 + 0.5f) / width - 1.f) * thf * aspect;      /* left <= right */
+    const float nya = (1.f - 2.f * (16 * ty + 0.5f) / height) * thf, nyb = (1.f - 2.f * (y1 + 0.5f) / height) * thf;                        /* top >= bottom */
+    keep = !(nxa * qz - qx > pad * sqrtf(1.f + nxa * nxa) || qx - nxb * qz > pad * sqrtf(1.f + nxb * nxb) ||
+             qy - nya * qz > pad * sqrtf(1.f + nya * nya) || nyb * qz - qy > pad * sqrtf(1.f + nyb * nyb));
+  }
+  const unsigned long long bal = __ballot(keep);
+  if (lane == 0) wcnt[wave] = __popcll(bal);
+  __syncthreads();
+  int before = 0, nl = 0;
+  for (int w = 0; w < 4; w++) { const int c = wcnt[w]; before += w < wave ? c : 0; nl += c; }
+  if (keep) list[before + __popcll(bal & ((1ull << lane) - 1ull))] = tid;
+  __syncthreads();
+  for (int i = tid; i < nl * RC_STRIDE; i += 256) { const int r = i / RC_STRIDE; T[i] = G[list[r] * RC_STRIDE + (i - r * RC_STRIDE)]; }
+  __syncthreads();
+  const int px = 16 * tx + (tid & 15), py = 16 * ty + (tid >> 4);
+  if (px >= width || py >= height) return;
+  const float nx = (2.f * (px + 0.5f) / width - 1.f) * thf * aspect, ny = (1.f - 2.f * (py + 0.5f) / height) * thf;
+  V3 d = fwd + right * nx + up * ny;
+  d = d * (1.f / norm(d));
+  const float far = 10.f;
+  float best = far, gbest = far; V3 bn = mk3(0, 0, 1), gn = bn; int bi = -1, gi = -1;
+  for (int c = 0; c < nl; c++) {
+    const float* rec = &T[c * RC_STRIDE];
+    const int tw = __float_as_int(rec[18]);
+    float t; V3 nn;
+    const int ci = __float_as_int(rec[19]) & 0xFF;
+    const bool hit = (tw & RC_HULL) ? rc_ray_hull(rec, (const float4*)m->hpl + m->hpl_off[ci], m->hpl_cnt[ci], eye, d, far, t, nn)
+                                    : ((tw & 0xFF) == 0 ? rc_ray_box(rec, eye, d, far, t, nn) : rc_ray_sphere(rec, eye, d, far, t, nn));
+    if (!hit) continue;
+    if (tw & RC_GHOST) { if (t < gbest) { gbest = t; gn = nn; gi = c; } }
+    else if (t < best) { best = t; bn = nn; bi = c; }
+  }
+  const size_t pix = (size_t)slot * width * height + (size_t)py * width + px;
+  if (rgb) {
+    const V3 light = mk3(0.2672612f, -0.5345225f, 0.8017837f);
+    auto shade = [&](int c, V3 nn) {
+      const float* rec = &T[c * RC_STRIDE];
+      const float k = 0.45f + 0.55f * fmaxf(0.f, dot(nn, light));
+      return mk3(rec[15] * k, rec[16] * k, rec[17] * k);
+    };
+    V3 colr = mk3(0.82f, 0.88f, 0.96f);
+    if (bi >= 0) colr = shade(bi, bn);
+    if (gi >= 0 && gbest < best) colr = colr * 0.5f + shade(gi, gn) * 0.5f;
+    unsigned char* o = rgb + pix * 3;
+    o[0] = (unsigned char)(fminf(fmaxf(colr.x, 0.f), 1.f) * 255.f + 0.5f);
+    o[1] = (unsigned char)(fminf(fmaxf(colr.y, 0.f), 1.f) * 255.f + 0.5f);
+    o[2] = (unsigned char)(fminf(fmaxf(colr.z, 0.f), 1.f) * 255.f + 0.5f);
+  }
+  if (depth) {
+    float tz = best;
+    if (bi >= 0) {      /* a sphere's hit parameter again, well conditioned: rc_ray_sphere's b b - 4 a c cancels at a grazing ray (to 1.5e-7 out of two terms near 6 on the button's globe,
+                         * 3e-4 m of depth); through the point of closest approach the same root is t_c - sqrt(r r - |o - c + t_c d|^2), whose terms are of the size of r */
+      const float* rec = &T[bi * RC_STRIDE];
+      const int tw = __float_as_int(rec[18]);
+      if (!(tw & RC_HULL) && (tw & 0xFF) != 0) {
+        const V3 oc = eye - ld3(rec + 9);
+        const float tc = -dot(oc, d);
+        const V3 perp = oc + d * tc;
+        tz = tc - sqrtf(fmaxf(rec[12] * rec[12] - dot(perp, perp), 0.f));
+      }
+    }
+    const float z = tz * dot(d, fwd);
+    depth[pix] = bi < 0 ? (metres ? far_plane : 1.f) : (metres ? z : fminf(fmaxf(far_plane * (z - near_plane) / (z * (far_plane - near_plane)), 0.f), 1.f));
+  }
+  if (seg) {
+    const int id = bi >= 0 ? __float_as_int(T[bi * RC_STRIDE + 19]) : 0;
+    seg[pix] = bi >= 0 ? ((id & 0xFF) | (((id >> 8) + 1) << 24)) : -1;
+  }
 }
 
 /* rayTest (environments.py:738-741) for K rays per env: from / to [num][K][3]; fraction 1 and collider -1 on a miss */

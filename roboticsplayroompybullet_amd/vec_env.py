@@ -177,6 +177,43 @@ def check_actuation_values(what, v):
     return _check_values(what, v, *ACTUATION_RANGES[what])
 
 
+def camera_rows(target=(0.0, 0.25, 0.0), distance=1.3, yaw=-30.0, pitch=-30.0, roll=0.0, fov=50.0, aspect=1.0, n=None):
+    """rp_render_layers' cam_rows on the host: a float32 CPU tensor [n, 11] of rows eye[3] target[3] up[3] fov_deg aspect.  Every argument is a scalar or a
+    length-n sequence / array / CPU tensor (target: [3] or [n, 3]); n is the longest of them unless given.  Eye and up as rp_camera_from_yaw_pitch_roll computes
+    them (float32 arguments, float64 trigonometry, float32 results).  ValueError unless every value is finite, 0 < fov < 180, aspect > 0 and distance > 0."""
+    cols = {'distance': distance, 'yaw': yaw, 'pitch': pitch, 'roll': roll, 'fov': fov, 'aspect': aspect}
+    cols = {k: _check_values('cameras: ' + k, v).reshape(-1) for k, v in cols.items()}
+    tg = _check_values('cameras: target', target)
+    if tg.dim() not in (1, 2) or tg.shape[-1] != 3:
+        raise ValueError('cameras: target is [3] or [n, 3], not %s' % (tuple(tg.shape),))
+    tg = tg.reshape(-1, 3)
+    lengths = {int(t.shape[0]) for t in list(cols.values()) + [tg]} - {1}
+    if n is None:
+        n = max(lengths) if lengths else 1
+    if lengths - {int(n)}:
+        raise ValueError('cameras: arguments of lengths %s for %d rows' % (sorted(lengths), n))
+    cols = {k: t.expand(n) for k, t in cols.items()}
+    tg = tg.expand(n, 3)
+    if not bool(((cols['fov'] > 0) & (cols['fov'] < 180)).all()):
+        raise ValueError('cameras: fov must lie in (0, 180) degrees')
+    if not bool((cols['aspect'] > 0).all()) or not bool((cols['distance'] > 0).all()):
+        raise ValueError('cameras: aspect and distance must be > 0')
+    d2r = 0.01745329251994329547
+    y, p, r = (cols[k].double() * d2r for k in ('yaw', 'pitch', 'roll'))
+    cy, sy, cp, sp, cr, sr = torch.cos(y), torch.sin(y), torch.cos(p), torch.sin(p), torch.cos(r), torch.sin(r)
+    back = torch.stack([cy * sr * sp - sy * cp, sy * sr * sp + cy * cp, cr * sp], 1)      # R's middle column, R = Rz(yaw) Ry(roll) Rx(pitch)
+    up = torch.stack([cy * sr * cp + sy * sp, sy * sr * cp - cy * sp, cr * cp], 1)        # ... and its last
+    eye = tg + (back * (-cols['distance']).double()[:, None]).float()
+    return torch.cat([eye, tg, up.float(), cols['fov'][:, None], cols['aspect'][:, None]], 1).contiguous()
+
+
+def unpack_segmentation(segmentation):
+    """(collider, link) of an rp_render_layers segmentation tensor or array (collider | (link + 1) << 24, -1 on a miss): collider -1 on a miss, link the Bullet
+    link index of an arm collider and -1 otherwise - what ray_test reports for the pixel's ray"""
+    hit = segmentation >= 0
+    return (segmentation & 0xFFFFFF) * hit - (~hit) * 1, (segmentation >> 24) * hit - 1
+
+
 class VecPlayEnv:
     def __init__(self, env_id, num_envs, device=0, seed=0, env_offset=0, action_type=None, goal_range_low=None, goal_range_high=None,
                  obj_lower_bound=None, obj_upper_bound=None, env_range_high=None, sparse_rew_thresh=None, sparse=True,
@@ -742,6 +779,57 @@ class VecPlayEnv:
             return img
         self._call('rp_render', C.byref(camera) if camera is not None else None, int(width), int(height), lo, n, _ptr(img), sg, self._stream())
         return img
+
+    def cameras(self, target=(0.0, 0.25, 0.0), distance=1.3, yaw=-30.0, pitch=-30.0, roll=0.0, fov=50.0, aspect=1.0):
+        """per-env cameras for render_layers(cameras=...): the float32 device tensor [n, 11] of camera_rows (each argument a scalar or a length-n host array or
+        tensor; all scalars: n = num_envs).  Host values are range-checked (ValueError): 0 < fov < 180, aspect > 0, distance > 0.  A tensor of the same layout built
+        on the device goes to render_layers as it is, unchecked and unread."""
+        scalars = all(torch.as_tensor(v).dim() == 0 for v in (distance, yaw, pitch, roll, fov, aspect)) and torch.as_tensor(target).dim() == 1
+        return camera_rows(target, distance, yaw, pitch, roll, fov, aspect, n=self.num_envs if scalars else None).to(self.device)
+
+    unpack_segmentation = staticmethod(unpack_segmentation)
+
+    def render_layers(self, width=200, height=200, envs=None, camera=None, cameras=None, layers=('rgb', 'depth', 'segmentation'), depth='buffer', near=0.01,
+                      far=10.0, sub_goal=None, ghost_arm=None, out=None):
+        """the layers of getCameraImage for envs [lo, hi) (default: all) as a dict of device tensors: 'rgb' uint8 [n, height, width, 3] (render's image, byte for
+        byte), 'depth' float32 [n, height, width] (depth='buffer': PyBullet's depthBuffer in [0, 1] for near / far, 1 on a miss; 'metres': eye-space z, far on a
+        miss), 'segmentation' int32 [n, height, width] (-1 on a miss, else collider | (link + 1) << 24: unpack_segmentation).  camera: an rp_camera for all envs
+        (self.camera(...)), or cameras: a float32 device tensor [n, 11], one row per env (self.cameras(...)) - not both.  Ghosts (sub_goal, ghost_arm: as render's)
+        tint rgb only.  out: a dict of preallocated tensors for some or all of the layers.  near / far shape the depth value only.  Nothing is read back."""
+        lo, hi = (0, self.num_envs) if envs is None else (int(envs[0]), int(envs[1]))
+        n, width, height = hi - lo, int(width), int(height)
+        layers = (layers,) if isinstance(layers, str) else tuple(layers)
+        shapes = {'rgb': ((n, height, width, 3), torch.uint8), 'depth': ((n, height, width), torch.float32), 'segmentation': ((n, height, width), torch.int32)}
+        if not layers or any(k not in shapes for k in layers):
+            raise ValueError('render_layers: layers are a non-empty choice of %s, not %r' % (sorted(shapes), layers))
+        if depth not in ('buffer', 'metres'):
+            raise ValueError("render_layers: depth is 'buffer' or 'metres', not %r" % (depth,))
+        if camera is not None and cameras is not None:
+            raise ValueError('render_layers: camera or cameras, not both')
+        if not (float(near) > 0.0 and float(far) > float(near)):
+            raise ValueError('render_layers: 0 < near < far, not near = %r, far = %r' % (near, far))
+        if cameras is not None:
+            if not (cameras.is_cuda and cameras.dtype == torch.float32 and tuple(cameras.shape) == (n, 11)):
+                raise ValueError('render_layers: cameras is a float32 device tensor [%d, 11], not %s %s on %s' % (n, cameras.dtype, tuple(cameras.shape), cameras.device))
+            cameras = cameras.contiguous()
+        res = {}
+        for k in layers:
+            shape, dtype = shapes[k]
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=self.device)
+            assert t.shape == shape and t.dtype == dtype and t.is_contiguous() and t.is_cuda, (k, t.shape, t.dtype)
+            res[k] = t
+        if sub_goal is not None:
+            sub_goal = sub_goal.to(device=self.device, dtype=torch.float32).contiguous()
+            assert sub_goal.shape == (n, self.dims['achieved_goal']), sub_goal.shape
+        if ghost_arm is not None:
+            ghost_arm = ghost_arm.to(device=self.device, dtype=torch.float32).contiguous()
+            assert ghost_arm.shape == (n, 8), ghost_arm.shape
+        self._call('rp_render_layers', C.byref(camera) if camera is not None else None, _ptr(cameras), float(near), float(far),
+                   _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, lo, n, _ptr(res.get('rgb')), _ptr(res.get('depth')),
+                   _ptr(res.get('segmentation')), _ptr(sub_goal), _ptr(ghost_arm), self._stream())
+        return res
 
     def ray_test(self, ray_from, ray_to):
         """bullet_client.rayTest for k rays per env: ray_from / ray_to [N, k, 3] (world).  Returns dict(hit_fraction [N, k] (1 = miss),
