@@ -220,7 +220,7 @@ int rp_set_state(rp_handle h, const void* src, int32_t src_env_count, void* stre
 typedef struct rp_camera {
   float eye[3], target[3], up[3];   /* computeViewMatrix(eye, target, up) */
   float fov_deg, aspect;            /* computeProjectionMatrixFOV(fov, aspect, near, far); near / far only clip: rays run 0 .. 10 m */
-  int32_t mode;                     /* 0 = this camera; 1 = gripper camera (ENV:33-49): eye at the EE link, looking along its -z, up = its x */
+  int32_t mode;                     /* 0 = this camera; 1 = gripper camera (ENV:33-49): eye at the EE link; with (roll, pitch, yaw) the link's Euler angles it looks along Rz(yaw) Ry(pitch) z, up = Rz(yaw) Ry(pitch) (-cos roll, -sin roll, 0) */
 } rp_camera;
 /* the reference's fixed camera (ENV:21-30): computeViewMatrixFromYawPitchRoll(target [0, 0.25, 0], distance 1.3, yaw -30, pitch -30, roll 0,
  * upAxisIndex 2), computeProjectionMatrixFOV(fov 50, aspect 1, near 0.01, far 10) */

@@ -177,6 +177,22 @@ __device__ __forceinline__ bool rc_ray_sphere(const float* rec, V3 o, V3 d, floa
   return true;
 }
 
+/* gripper_camera (environments.py:33-49) from the EE link's rotation R: ori = the link's Euler angles + (0, -pi / 2, 0), rot = the matrix of ori's quaternion, camera
+ * vector = rot (1, 0, 0), up vector = rot (0, 0, 1), then computeViewMatrix(pos, pos + camera vector, up vector): f = the camera vector, s = f x up normalised, u = s x f.
+ * With (roll, pitch, yaw) the link's angles this is f = Rz(yaw) Ry(pitch) z and u = Rz(yaw) Ry(pitch) (-cos roll, -sin roll, 0) - NOT a fixed rotation of the link frame: it
+ * is the link's (-z, +x) only at roll = pi (what rounds 3 to 6 drew for every pose) and (+z, -x) at roll = 0, the reset pose.  The operations are the reference's own, one by
+ * one with the library's conversions, so that both render kernels hold the same bits. */
+__device__ __forceinline__ void rc_gripper_basis(const M3& R, V3& fwd, V3& right, V3& up) {
+  const Q4 q = m3_to_quat(R);
+  const V3 e = euler_from_quat(q.x, q.y, q.z, q.w);
+  const M3 rot = quat_to_m3(quat_from_euler(e.x, e.y - 0.5f * RP_PI_F, e.z));
+  const V3 f = col(rot, 0), u0 = col(rot, 2);
+  fwd = f * (1.f / norm(f));
+  const V3 s = cross(fwd, u0);
+  right = s * (1.f / norm(s));
+  up = cross(right, fwd);
+}
+
 /* obs['img'] (environments.py:841-845): one thread per pixel, row 0 = top of the image, uint8 rgb */
 __global__ void __launch_bounds__(256) k_render(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, int num, RpCamera cam, const float* __restrict__ ee_pose,
                                                 int width, int height, unsigned char* __restrict__ rgb) {
@@ -191,12 +207,10 @@ __global__ void __launch_bounds__(256) k_render(const DevModel* __restrict__ m, 
   if (pix >= width * height) return;
   const int px = pix % width, py = pix / width;
   V3 eye = ld3(cam.eye), fwd = ld3(cam.fwd), right = ld3(cam.right), up = ld3(cam.up);
-  if (cam.mode == 1) {       /* gripper_camera (environments.py:33-49): at the EE link, looking along its x axis pitched by -90 deg, up = its z */
+  if (cam.mode == 1) {       /* gripper_camera (environments.py:33-49): at the EE link, the reference's basis from the link's Euler angles */
     const float* e = ee_pose + 12 * slot;
-    const M3 R = ldm3(e + 3);
     eye = ld3(e);
-    /* ori = euler(link) + (0, -pi/2, 0) in the reference; restated as the link frame's axes: forward = -z, up = x */
-    fwd = col(R, 2) * -1.f; up = col(R, 0); right = cross(fwd, up);
+    rc_gripper_basis(ldm3(e + 3), fwd, right, up);
   }
   const float nx = (2.f * (px + 0.5f) / width - 1.f) * cam.tan_half_fov * cam.aspect, ny = (1.f - 2.f * (py + 0.5f) / height) * cam.tan_half_fov;
   V3 d = fwd + right * nx + up * ny;
@@ -276,9 +290,8 @@ __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restric
       V3 eye = ld3(cam.eye), fwd = ld3(cam.fwd), right = ld3(cam.right), up = ld3(cam.up);
       if (cam.mode == 1) {       /* gripper_camera, as in k_render */
         const float* e = ee_pose + 12 * slot;
-        const M3 R = ldm3(e + 3);
         eye = ld3(e);
-        fwd = col(R, 2) * -1.f; up = col(R, 0); right = cross(fwd, up);
+        rc_gripper_basis(ldm3(e + 3), fwd, right, up);
       }
       st3(V, eye); st3(V + 3, fwd); st3(V + 6, right); st3(V + 9, up);
       V[12] = cam.tan_half_fov; V[13] = cam.aspect;

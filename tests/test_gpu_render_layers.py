@@ -8,7 +8,8 @@ import pytest
 
 torch = pytest.importorskip('torch')
 
-from test_gpu_render import cast, default_camera, oracle_hulls      # noqa: E402
+from camera_cases import cast, oracle_hulls, pixel_rays      # noqa: E402
+from test_gpu_render import default_camera      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 U, V, W2 = 'UR5PlayAbsRPY1Obj-v0', 'pandaPlayAbsRPY1Obj-v0', 'pandaPlay-v0'
@@ -61,20 +62,6 @@ def both_ways(env, **kw):
     finally:
         cull(env, True)
     return culled, plain
-
-
-def pixel_rays(eye, target, up, fov, aspect, w, h):
-    """eye-to-pixel-centre unit directions [h * w, 3] and the forward axis, float64 (reference_image's arithmetic)"""
-    f = (target - eye) / np.linalg.norm(target - eye)
-    s = np.cross(f, up)
-    s /= np.linalg.norm(s)
-    u = np.cross(s, f)
-    th = np.tan(0.5 * np.radians(fov))
-    px, py = np.meshgrid(np.arange(w), np.arange(h))
-    nx = (2 * (px.ravel() + 0.5) / w - 1) * th * aspect
-    ny = (1 - 2 * (py.ravel() + 0.5) / h) * th
-    d = f + nx[:, None] * s + ny[:, None] * u
-    return d / np.linalg.norm(d, axis=1, keepdims=True), f
 
 
 @pytest.mark.parametrize('name', CAMERAS)
