@@ -145,6 +145,15 @@ def load(f32=False, bullet_ref=False, abx=False):
     lib.rpo_bench_rollout.restype = C.c_double
     lib.rpo_rng_uniform.argtypes = [C.c_ulonglong, C.c_uint, C.c_uint]
     lib.rpo_rng_uniform.restype = C.c_double
+    lib.rpo_n_obj.argtypes = [vp]
+    lib.rpo_n_body.argtypes = [vp]
+    for name in ('friction', 'mass', 'wrench', 'gravity'):
+        getattr(lib, 'rpo_set_' + name).argtypes = [vp, dp]
+        getattr(lib, 'rpo_get_' + name).argtypes = [vp, dp]
+    lib.rpo_set_motor.argtypes = [vp, dp, dp]
+    lib.rpo_get_motor_factors.argtypes = [vp, dp, dp]
+    lib.rpo_last_rows.argtypes = [vp, dp, C.c_int]
+    lib.rpo_contact_mu.argtypes = [vp, dp, C.c_int]
     if bullet_ref:
         lib.rpo_set_ref_flags.argtypes = [vp, C.c_uint]
         lib.rpo_get_ref_flags.argtypes = [vp]
@@ -218,6 +227,7 @@ class OracleEnv:
             self.lib.rpo_set_reward_cfg(self.h, 0.05 if sparse_rew_thresh is None else float(sparse_rew_thresh), int(bool(dense_reward)))
         self.n_arm = self.lib.rpo_n_arm(self.h)
         self.nv = self.lib.rpo_nv(self.h)
+        self.n_free = (self.lib.rpo_state_size(self.h) - 2 * self.n_arm) // 13
         self.n_goal = {0: 11, 4: 11, 5: 18}.get(self.kind, 3)
         self.n_target = 7 if self.kind in (2, 3, 4, 5) else 6
 
@@ -410,6 +420,75 @@ class OracleEnv:
         self.lib.rpo_get_motor(self.h, mode.ctypes.data_as(C.POINTER(C.c_int)), tgt.ctypes.data_as(C.POINTER(C.c_double)),
                                mx.ctypes.data_as(C.POINTER(C.c_double)))
         return mode, tgt, mx
+
+    # ---- the instance's parameters: one row of the HIP library's per-env tables, in the column orders of vec_env.dynamics_names / wrench_names / actuation_names
+    def _set(self, what, fn, *vals):
+        if fn(self.h, *[_d(v)[1] if v is not None else None for v in vals]) != 0:
+            raise ValueError('%s refused (a value out of range, or a build that has no parameters)' % what)
+
+    def _get(self, fn, *sizes):
+        outs = [np.zeros(k) for k in sizes]
+        fn(self.h, *[o.ctypes.data_as(C.POINTER(C.c_double)) for o in outs])
+        return outs
+
+    def set_dynamics(self, friction=None, mass=None):
+        """lateral friction per collision object [n_obj] and / or mass per free body [n_free]; None leaves that parameter as it is"""
+        if friction is not None:
+            f = np.asarray(friction, dtype=np.float64).reshape(-1)
+            assert len(f) == self.lib.rpo_n_obj(self.h), len(f)
+            self._set('friction', self.lib.rpo_set_friction, f)
+        if mass is not None and self.n_free:
+            m = np.asarray(mass, dtype=np.float64).reshape(-1)
+            assert len(m) == self.n_free, len(m)
+            self._set('mass', self.lib.rpo_set_mass, m)
+
+    def get_dynamics(self):
+        fr, = self._get(self.lib.rpo_get_friction, self.lib.rpo_n_obj(self.h))
+        ms, = self._get(self.lib.rpo_get_mass, max(self.n_free, 1))
+        return {'friction': fr, 'mass': ms[:self.n_free]}
+
+    def set_wrench(self, wrench=None):
+        """[n_body, 6] world force and torque per moving body (arm links in dof order, free bodies, scene-joint bodies); None: zero"""
+        nb = self.lib.rpo_n_body(self.h)
+        w = np.zeros((nb, 6)) if wrench is None else np.asarray(wrench, dtype=np.float64)
+        assert w.shape == (nb, 6), w.shape
+        self._set('wrench', self.lib.rpo_set_wrench, w)
+
+    def get_wrench(self):
+        nb = self.lib.rpo_n_body(self.h)
+        return self._get(self.lib.rpo_get_wrench, 6 * nb)[0].reshape(nb, 6)
+
+    def set_actuation(self, gravity=None, motor_gain=None, motor_strength=None):
+        """gravity [3], motor_gain [n_arm], motor_strength [n_arm]; None leaves that parameter as it is"""
+        if gravity is not None:
+            g = np.asarray(gravity, dtype=np.float64).reshape(-1)
+            assert len(g) == 3
+            self._set('gravity', self.lib.rpo_set_gravity, g)
+        if motor_gain is not None or motor_strength is not None:
+            kg = None if motor_gain is None else np.asarray(motor_gain, dtype=np.float64).reshape(-1)
+            ks = None if motor_strength is None else np.asarray(motor_strength, dtype=np.float64).reshape(-1)
+            assert all(v is None or len(v) == self.n_arm for v in (kg, ks))
+            self._set('motor gain / strength', self.lib.rpo_set_motor, kg, ks)
+
+    def get_actuation(self):
+        g, = self._get(self.lib.rpo_get_gravity, 3)
+        kg, ks = self._get(self.lib.rpo_get_motor_factors, self.n_arm, self.n_arm)
+        return {'gravity': g, 'motor_gain': kg, 'motor_strength': ks}
+
+    ROW_FIELDS = ('utype', 'dof', 'fric_parent', 'rhs', 'lo', 'hi', 'dinv', 'lambda', 'mu')
+
+    def last_rows(self):
+        """[n_rows, 9] the rows of the latest substep after its solve, columns ROW_FIELDS (a friction or torsional row is bounded by -+ mu lambda[fric_parent])"""
+        out = np.zeros((160, 9))
+        n = self.lib.rpo_last_rows(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), 160)
+        assert n <= 160, n
+        return out[:n]
+
+    def contact_mu(self):
+        """the friction coefficient of every contact of the latest contact list (contacts()' order)"""
+        out = np.zeros(96)
+        n = self.lib.rpo_contact_mu(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), 96)
+        return out[:n]
 
     def set_goal(self, goal):
         self.lib.rpo_set_goal(self.h, _d(goal)[1])

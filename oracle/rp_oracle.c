@@ -110,6 +110,11 @@ struct rpo_env {
   real fpos[RP_MAX_FREE][3], fquat[RP_MAX_FREE][4], fvel[RP_MAX_FREE][3], fom[RP_MAX_FREE][3];
   real jq[RP_MAX_J1], jqd[RP_MAX_J1];
   int mmode[RP_MAX_ARM]; real mtarget[RP_MAX_ARM], mmaximp[RP_MAX_ARM];
+  /* the instance's parameters (rpo_set_friction .. rpo_set_motor; the HIP library's per-env tables): no reset touches them, the state calls do not carry them.  Friction
+   * and mass live in the private model above (m.col_friction, m.free_mass); mass0 keeps the baked mass, which the inertia scales by.  Defaults: the bake, zero
+   * wrenches, (0, 0, GRAVITY), ones, ones - and with them every expression below rounds as it did with the constants */
+  real mass0[RP_MAX_FREE], grav[3], mgain[RP_MAX_ARM], mstrength[RP_MAX_ARM];
+  real wrench[RP_MAX_ARM + RP_MAX_FREE + RP_MAX_J1][6];      /* world force through the centre of mass, world torque: arm links in dof order, free bodies, scene-joint bodies */
   real goal[18]; int n_goal;
   real last_obs[26], last_ag[18]; int have_last;
   /* config flags (envList.py) */
@@ -946,6 +951,9 @@ static int hull_box_gjk(rpo_env* e, int hc, int bc, real margin, const real* lv,
 static void pm_to_local(const rpo_env* e, int body, const real* pw, real* pl) { real t[3]; v3sub(t, pw, e->xb[body].p); m3tmulv(pl, e->xb[body].R, t); }
 static void pm_to_world(const rpo_env* e, int body, const real* pl, real* pw) { m3mulv(pw, e->xb[body].R, pl); v3add(pw, pw, e->xb[body].p); }
 static void solver_order(rpo_env* e);
+/* friction of a contact between colliders a and b: the product of the two objects' lateral frictions (the instance's: rpo_set_friction), at most 10 - Bullet's
+ * MAX_FRICTION in btManifoldResult::calculateCombinedFriction.  No baked pair reaches the bound */
+static inline real pair_mu(const rp_model* m, int a, int b) { const real mu = (real)(m->col_friction[a] * m->col_friction[b]); return mu > (real)10 ? (real)10 : mu; }
 /* the torsional rows the contact list asks for before the MAX_TORS cut (build_rows' rule: one per run of contacts of one collider pair with spinning friction) */
 static void count_tors(rpo_env* e) {
   const rp_model* m = &e->m;
@@ -1146,7 +1154,7 @@ static void collide_persistent(rpo_env* e) {
       c->ca = e->pm[mi].pt[i].ca; c->cb = e->pm[mi].pt[i].cb;
       for (int k = 0; k < 3; k++) { c->p[k] = (real)0.5 * (e->pm[mi].pt[i].pA[k] + e->pm[mi].pt[i].pB[k]); c->n[k] = e->pm[mi].pt[i].n[k]; }
       c->dist = e->pm[mi].pt[i].dist;
-      c->mu = (real)(m->col_friction[c->ca] * m->col_friction[c->cb]);
+      c->mu = pair_mu(m, c->ca, c->cb);
     }
   }
   if (!(e->rule & RPO_RULE_CREATION_ORDER)) solver_order(e);
@@ -1243,7 +1251,7 @@ static void collide(rpo_env* e) {
       c.ca = a; c.cb = b;
       v3cpy(c.p, pts[i].p); v3cpy(c.n, pts[i].n);
       c.dist = pts[i].dist;
-      c.mu = (real)(m->col_friction[a] * m->col_friction[b]);
+      c.mu = pair_mu(m, a, b);
       if (single) {
         if (nman == 0) man[nman++] = c;
         else if (c.dist < man[0].dist - TIE_EPS) man[0] = c;
@@ -1327,6 +1335,14 @@ static void arm_aba(rpo_env* e, real* qdd) {
     real Iv[6];
     m6mulv(Iv, e->IA[i], e->vsp[i]);
     crf(pA[i], e->vsp[i], Iv);
+    /* the link's external wrench: a force f through its centre of mass and a torque t are the spatial force (t + com x f, f) about the world origin, which the link's
+     * bias force loses - so that the joint torques change by -J_com^T f - J_w^T t */
+    const real* w = e->wrench[i];
+    if (w[0] != 0 || w[1] != 0 || w[2] != 0 || w[3] != 0 || w[4] != 0 || w[5] != 0) {
+      real cxf[3];
+      v3cross(cxf, com, w);
+      for (int k = 0; k < 3; k++) { pA[i][k] -= w[3 + k] + cxf[k]; pA[i][3 + k] -= w[k]; }
+    }
   }
   real u[RP_MAX_ARM];
   for (int i = n - 1; i >= 0; i--) {
@@ -1348,7 +1364,11 @@ static void arm_aba(rpo_env* e, real* qdd) {
     int p = m->arm_parent[i];
     real ap[6];
     for (int k = 0; k < 6; k++) ap[k] = (p >= 0 ? a[p][k] : 0) + c[i][k];
-    if (p < 0) ap[5] += -GRAVITY;      /* fictitious base acceleration = -g */
+    if (p < 0) {                       /* fictitious base acceleration = -g */
+      ap[5] += -e->grav[2];
+      if (e->grav[0] != 0) ap[3] += -e->grav[0];
+      if (e->grav[1] != 0) ap[4] += -e->grav[1];
+    }
     qdd[i] = (u[i] - dot6(e->U[i], ap)) / e->D[i];
     for (int k = 0; k < 6; k++) a[i][k] = ap[k] + e->S[i][k] * qdd[i];
   }
@@ -1518,9 +1538,11 @@ static void build_rows(rpo_env* e, const real* vstar) {
         r->J[i] = 1;
         arm_impulse_response(e, -1, 0, tau, r->B);
         r->dinv = 1 / r->B[i];
-        real des = e->mmode[i] ? MOTOR_KP * (e->mtarget[i] - e->q[i]) / DT : 0;   /* kp*err/dt + qd + kd*(0-qd), kd = 1 */
+        /* kp*err/dt + qd + kd*(0-qd), kd = 1; the instance's gain scales kp and its strength the impulse bound the action gave the motor (rpo_set_motor) */
+        real des = e->mmode[i] ? MOTOR_KP * e->mgain[i] * (e->mtarget[i] - e->q[i]) / DT : 0;
+        const real maximp = e->mmaximp[i] * e->mstrength[i];
         r->rhs = (des - vstar[i]) * r->dinv;
-        r->lo = -e->mmaximp[i]; r->hi = e->mmaximp[i];
+        r->lo = -maximp; r->hi = maximp;
       }
     } else if (what == 1) { /* scene joint motors: button position motor (scenes.py:238), default velocity motors on door and dial */
       for (int k = 0; k < m->n_joint1; k++) {
@@ -1819,9 +1841,19 @@ static void substep_unconstrained(rpo_env* e, real* vstar) {
     const xform* x = &e->xb[1 + m->n_arm + k];
     real vn = v3norm(e->fvel[k]);
     for (int i = 0; i < 3; i++) vstar[d + i] = e->fvel[k][i] + DT * (-(FREE_LIN_DAMP + FREE_LIN_DAMP * vn) * e->fvel[k][i]);
-    vstar[d + 2] += DT * GRAVITY;
+    vstar[d + 2] += DT * e->grav[2];
+    const real* w = e->wrench[m->n_arm + k];
+    for (int i = 0; i < 3; i++) {
+      if (i < 2 && e->grav[i] != 0) vstar[d + i] += DT * e->grav[i];
+      if (w[i] != 0) vstar[d + i] += DT * w[i] / (real)m->free_mass[k];      /* the force over the instance's mass */
+    }
     memset(e->finv[k], 0, sizeof(e->finv[k]));
     if (!m->free_rot_locked[k]) {
+      /* the inertia the contacts and torques meet is the baked one times mass / baked mass (a body of the same shape and uniform density); the gyroscopic and
+       * damping accelerations below are ratios of inertias, so they keep the baked one */
+      const real scale = (real)m->free_mass[k] / e->mass0[k];
+      real Is[3];
+      for (int i = 0; i < 3; i++) Is[i] = (real)m->free_inertia[k][i] * scale;
       /* local frame: alpha = I^-1 ( -(w x I w) - I w (k1 + k2 |w|) ) */
       real wl[3], Iw[3], g[3], al[3], aw[3];
       m3tmulv(wl, x->R, e->fom[k]);
@@ -1833,21 +1865,35 @@ static void substep_unconstrained(rpo_env* e, real* vstar) {
       for (int i = 0; i < 3; i++) vstar[d + 3 + i] = e->fom[k][i] + DT * aw[i];
       for (int r = 0; r < 3; r++) for (int s = 0; s < 3; s++) {
         real v = 0;
-        for (int t = 0; t < 3; t++) v += x->R[3 * r + t] * x->R[3 * s + t] / (real)m->free_inertia[k][t];
+        for (int t = 0; t < 3; t++) v += x->R[3 * r + t] * x->R[3 * s + t] / Is[t];
         e->finv[k][3 * r + s] = v;
+      }
+      if (w[3] != 0 || w[4] != 0 || w[5] != 0) {      /* torque: R Is^-1 R^T t */
+        real tl[3], tw[3];
+        m3tmulv(tl, x->R, w + 3);
+        for (int i = 0; i < 3; i++) tl[i] /= Is[i];
+        m3mulv(tw, x->R, tl);
+        for (int i = 0; i < 3; i++) vstar[d + 3 + i] += DT * tw[i];
       }
     }
   }
   for (int k = 0; k < m->n_joint1; k++) {
     int d = dof_j1(e, k);
+    real ax[3], a[3];
+    for (int i = 0; i < 3; i++) ax[i] = (real)m->j1_axis[k][i];
+    m3mulv(a, e->xb[1 + m->n_arm + m->n_free + k].R, ax);
     if (m->j1_type[k] == 1) {
-      real ax[3], a[3];
-      for (int i = 0; i < 3; i++) ax[i] = (real)m->j1_axis[k][i];
-      m3mulv(a, e->xb[1 + m->n_arm + m->n_free + k].R, ax);
-      vstar[d] = e->jqd[k] + DT * GRAVITY * a[2];
+      vstar[d] = e->jqd[k] + DT * e->grav[2] * a[2];
+      if (e->grav[0] != 0 || e->grav[1] != 0) vstar[d] += DT * R_FMA(a[1], e->grav[1], a[0] * e->grav[0]);
     } else {
       real w = e->jqd[k];
       vstar[d] = w + DT * (-(J1_ANG_DAMP + J1_ANG_DAMP * R_FABS(w)) * w);
+    }
+    /* the body's wrench: its force along a prismatic joint's world axis, its torque about a revolute joint's, times the joint's inverse mass / inertia */
+    const real* wj = e->wrench[m->n_arm + m->n_free + k] + (m->j1_type[k] == 1 ? 0 : 3);
+    if (wj[0] != 0 || wj[1] != 0 || wj[2] != 0) {
+      const real minv = m->j1_type[k] == 1 ? 1 / (real)m->j1_mass[k] : 1 / (real)m->j1_inertia_axis[k];
+      vstar[d] += DT * (v3dot(a, wj) * minv);
     }
   }
 }
@@ -1986,7 +2032,7 @@ static int collide_persist(rpo_env* e) {
       c.ca = st->man[i].ca; c.cb = st->man[i].cb;
       for (int k = 0; k < 3; k++) { c.p[k] = (real)0.5 * (p->pA[k] + p->pB[k]); c.n[k] = p->n[k]; }
       c.dist = p->dist;
-      c.mu = (real)(m->col_friction[c.ca] * m->col_friction[c.cb]);
+      c.mu = pair_mu(m, c.ca, c.cb);
       e->con[e->ncon++] = c;
     }
   }
@@ -2879,7 +2925,9 @@ rpo_env* rpo_create(int kind, unsigned long long seed, int env_index) {
     e->n_goal = 3;
   }
   /* initial state = as loaded: arm at q = 0, bodies at their creation poses, default velocity motors everywhere */
-  for (int i = 0; i < m->n_arm; i++) { e->mmode[i] = 0; e->mmaximp[i] = DEFAULT_MOTOR_MAXIMP; }
+  for (int i = 0; i < m->n_arm; i++) { e->mmode[i] = 0; e->mmaximp[i] = DEFAULT_MOTOR_MAXIMP; e->mgain[i] = 1; e->mstrength[i] = 1; }
+  e->grav[0] = 0; e->grav[1] = 0; e->grav[2] = GRAVITY;
+  for (int k = 0; k < m->n_free; k++) e->mass0[k] = (real)m->free_mass[k];
   for (int k = 0; k < m->n_free; k++) {
     real R0[9];
     for (int i = 0; i < 3; i++) e->fpos[k][i] = (real)m->free_pos0[k][i];
@@ -2954,6 +3002,63 @@ void rpo_shift_free_body(rpo_env* e, int k, double dx, double dy, double dz) {
 void rpo_get_motor(const rpo_env* e, int* mode, double* target, double* maximp) {
   for (int i = 0; i < e->m.n_arm; i++) { mode[i] = e->mmode[i]; target[i] = e->mtarget[i]; maximp[i] = e->mmaximp[i]; }
 }
+/* ---- the instance's parameters (the HIP library's per-env tables).  The setters return 0, or -1 where they refuse: the frozen reference step and
+ * the experiment build read the baked model and constants of their own */
+#if defined(RPO_BULLET_REF) || defined(RPO_ABX)
+#define RPO_PARAMS_REFUSED 1
+#else
+#define RPO_PARAMS_REFUSED 0
+#endif
+int rpo_n_obj(const rpo_env* e) { int n = 0; for (int c = 0; c < e->m.n_col; c++) if (e->m.col_obj[c] >= n) n = e->m.col_obj[c] + 1; return n; }
+int rpo_n_body(const rpo_env* e) { return e->m.n_arm + e->m.n_free + e->m.n_joint1; }
+int rpo_set_friction(rpo_env* e, const double* mu) {
+  if (RPO_PARAMS_REFUSED) return -1;
+  const int n = rpo_n_obj(e);
+  for (int o = 0; o < n; o++) if (!(mu[o] >= 0)) return -1;
+  for (int c = 0; c < e->m.n_col; c++) e->m.col_friction[c] = mu[e->m.col_obj[c]];
+  return 0;
+}
+void rpo_get_friction(const rpo_env* e, double* mu) { for (int c = e->m.n_col - 1; c >= 0; c--) mu[e->m.col_obj[c]] = e->m.col_friction[c]; }
+int rpo_set_mass(rpo_env* e, const double* mass) {
+  if (RPO_PARAMS_REFUSED) return -1;
+  for (int k = 0; k < e->m.n_free; k++) if (!(mass[k] > 0)) return -1;
+  for (int k = 0; k < e->m.n_free; k++) e->m.free_mass[k] = mass[k];
+  return 0;
+}
+void rpo_get_mass(const rpo_env* e, double* mass) { for (int k = 0; k < e->m.n_free; k++) mass[k] = e->m.free_mass[k]; }
+int rpo_set_wrench(rpo_env* e, const double* w) {
+  if (RPO_PARAMS_REFUSED) return -1;
+  for (int b = 0; b < rpo_n_body(e); b++) for (int k = 0; k < 6; k++) e->wrench[b][k] = (real)w[6 * b + k];
+  return 0;
+}
+void rpo_get_wrench(const rpo_env* e, double* w) { for (int b = 0; b < rpo_n_body(e); b++) for (int k = 0; k < 6; k++) w[6 * b + k] = e->wrench[b][k]; }
+int rpo_set_gravity(rpo_env* e, const double* g) {
+  if (RPO_PARAMS_REFUSED) return -1;
+  for (int k = 0; k < 3; k++) e->grav[k] = (real)g[k];
+  return 0;
+}
+void rpo_get_gravity(const rpo_env* e, double* g) { for (int k = 0; k < 3; k++) g[k] = e->grav[k]; }
+int rpo_set_motor(rpo_env* e, const double* gain, const double* strength) {      /* either may be NULL: left as it is */
+  if (RPO_PARAMS_REFUSED) return -1;
+  for (int i = 0; i < e->m.n_arm; i++) if ((gain && !(gain[i] >= 0)) || (strength && !(strength[i] >= 0))) return -1;
+  for (int i = 0; i < e->m.n_arm; i++) { if (gain) e->mgain[i] = (real)gain[i]; if (strength) e->mstrength[i] = (real)strength[i]; }
+  return 0;
+}
+void rpo_get_motor_factors(const rpo_env* e, double* gain, double* strength) { for (int i = 0; i < e->m.n_arm; i++) { gain[i] = e->mgain[i]; strength[i] = e->mstrength[i]; } }
+/* the rows of the latest substep after its solve, 9 numbers each: utype, the first dof the row acts on, fric_parent, rhs, lo, hi, dinv, lambda, mu (a friction or torsional
+ * row is bounded by -+ mu lambda[fric_parent], not by lo / hi).  Returns the number of rows */
+int rpo_last_rows(const rpo_env* e, double* out, int max) {
+  for (int i = 0; i < e->nrows && i < max; i++) {
+    const row* r = &e->rows[i];
+    int d = 0;
+    while (d < e->nv - 1 && r->J[d] == 0) d++;
+    double* o = out + 9 * i;
+    o[0] = r->utype; o[1] = d; o[2] = r->fric_parent; o[3] = r->rhs; o[4] = r->lo; o[5] = r->hi; o[6] = r->dinv; o[7] = r->lambda; o[8] = r->mu;
+  }
+  return e->nrows;
+}
+/* the friction coefficient of every contact of the latest contact list (rpo_contacts' order) */
+int rpo_contact_mu(const rpo_env* e, double* out, int max) { for (int i = 0; i < e->ncon && i < max; i++) out[i] = e->con[i].mu; return e->ncon; }
 void rpo_set_goal(rpo_env* e, const double* goal) { for (int k = 0; k < e->n_goal; k++) e->goal[k] = (real)goal[k]; }
 void rpo_clear_quat_memory(rpo_env* e) { e->have_last = 0; }
 

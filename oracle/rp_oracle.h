@@ -6,6 +6,10 @@
  * mapping, observation assembly, rewards, reset sampling) IS pinned against tests/golden JSON fixtures, which were
  * produced by executing the reference's own Python (tests/golden/make_goldens.py).
  *
+ * The domain-randomisation parameters of the HIP library (per-env friction, mass, wrenches, gravity, motor gain and strength) are parameters of an instance here
+ * (rpo_set_friction .. rpo_set_motor below): the reference has no such thing, their meaning is the library's, restated in this file's own terms and
+ * held by closed forms in tests/test_oracle_params.py.
+ *
  * One rpo_env = one reference `instance` + `playEnv` (environments.py:58-1073) without Python.
  * All I/O is double regardless of the internal `real` (build with -DRP_FLOAT for an fp32 oracle). */
 #ifndef RP_ORACLE_H
@@ -90,6 +94,35 @@ int rpo_state_size(const rpo_env*);
 void rpo_get_state(const rpo_env*, double* s);
 void rpo_set_state(rpo_env*, const double* s);
 void rpo_get_motor(const rpo_env*, int* mode, double* target, double* maximp);
+/* The instance's parameters: what the HIP library keeps per env in its dynamics, wrench and actuation tables (rp_set_dynamics, rp_set_wrench, rp_set_actuation).  A fresh
+ * instance has the baked frictions and masses, zero wrenches, gravity (0, 0, -9.8), gains and strengths 1, and with those every result is bit for bit what it was before the
+ * parameters existed.  No reset touches them; rpo_get_state / rpo_set_state do not carry them.
+ *   friction [rpo_n_obj]   lateral friction per collision object (rp_model.col_obj; all colliders of the object).  A contact's friction is min(mu_a mu_b, 10); a torsional
+ *                          row is bounded by spin_a mu_b + spin_b mu_a
+ *   mass [n_free]          a contact row's inverse mass is 1 / mass; the inertia that contacts and torques meet is the baked one times mass / baked mass; the gyroscopic and
+ *                          damping accelerations keep the baked inertia (they are ratios of inertias)
+ *   wrench [rpo_n_body][6] fx fy fz tx ty tz, world: the arm's links in dof order, the free bodies, the scene-joint bodies.  Enters the unconstrained velocities only:
+ *                          arm tau = tau0 - J_com^T f - J_w^T t; free body dt f / mass and dt R I^-1 R^T t; scene joint dt (axis_world . f or t) / (its mass or inertia)
+ *   gravity [3]            on the arm, the free bodies and the prismatic scene joints
+ *   gain, strength [n_arm] an arm motor asks for (0.1 gain) (target - q) / dt and is bounded by -+ (its impulse bound) strength; scene-joint motors, the finger gear and
+ *                          the limit rows do not read them
+ * The setters return 0, or -1 where a value is out of range (friction, gain, strength < 0; mass <= 0) and always in librp_oracle_bullet.so / librp_oracle_abx.so. */
+int rpo_n_obj(const rpo_env*);
+int rpo_n_body(const rpo_env*);
+int rpo_set_friction(rpo_env*, const double* mu);
+void rpo_get_friction(const rpo_env*, double* mu);
+int rpo_set_mass(rpo_env*, const double* mass);
+void rpo_get_mass(const rpo_env*, double* mass);
+int rpo_set_wrench(rpo_env*, const double* w);
+void rpo_get_wrench(const rpo_env*, double* w);
+int rpo_set_gravity(rpo_env*, const double* g3);
+void rpo_get_gravity(const rpo_env*, double* g3);
+int rpo_set_motor(rpo_env*, const double* gain, const double* strength);      /* either may be NULL: left as it is */
+void rpo_get_motor_factors(const rpo_env*, double* gain, double* strength);
+/* the rows of the latest substep after its solve, 9 numbers each: utype (1 motor, 2 limit, 0 other), first dof, fric_parent (-1: none), rhs, lo, hi, dinv, lambda, mu (a
+ * friction or torsional row is bounded by -+ mu lambda[fric_parent]); returns the number of rows */
+int rpo_last_rows(const rpo_env*, double* out, int max);
+int rpo_contact_mu(const rpo_env*, double* out, int max);      /* friction of every contact of the latest contact list, rpo_contacts' order */
 void rpo_set_goal(rpo_env*, const double* goal);
 void rpo_clear_quat_memory(rpo_env*);
 

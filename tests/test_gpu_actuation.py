@@ -1,6 +1,9 @@
 """Per-env gravity and arm-motor gain / strength (rp_set_actuation / VecPlayEnv.set_actuation).  Run with -m gpu on the MI355X box.
 
-The oracle's gravity and motor constants are fixed, so the feature is held by properties: the table's semantics; the default row moves no bit in any
+Gravity, gain and strength where they meet contacts - a held block under a tilted gravity, motor strength against a table, the motor rows that k_solve2 rebuilds in
+solve4_body, heavy_solve and super_solve - are held by tests/test_gpu_param_lockstep.py: the CPU oracle has gravity, gain and strength per instance (rpo_set_gravity,
+rpo_set_motor; their closed forms: tests/test_oracle_params.py) and follows the device step by step with the device's own table rows.  This file holds the table and the
+properties that need no oracle step: the table's semantics; the default row moves no bit in any
 pipeline; a free body in the air follows the substep recurrence under the env's own gravity, and agrees with the same change expressed as a wrench; the
 arm's bias torques change by -sum_i m_i J_com_i^T dg (the oracle's Jacobians); the drawer and the prismatic scene joints feel the component along their
 axis; strength 0 switches a motor off and a strength below / above the gravity torque lets a joint sag / hold; the gain follows e (1 - 0.1 gain)^12 as

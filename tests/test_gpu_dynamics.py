@@ -1,8 +1,10 @@
 """Per-env lateral friction and free-body mass (rp_set_dynamics / VecPlayEnv.set_dynamics).  Run with -m gpu on the MI355X box.
 
-The oracle runs the baked model only, so randomised envs are held by properties: baked values written back change no bit; an env's values reach that
-env and no other, in every pipeline and through every reset path; a block slides the distance its friction gives; a collision keeps the momentum its
-masses give.
+What holds the values themselves in contact - the pair friction of arm-link and cached-point contacts, the heavy path's friction bounds, the torsional bound, the
+clamp at 10, the inertia scale of a body that turns in contact - is tests/test_gpu_param_lockstep.py: the CPU oracle has the same parameters per instance
+(rpo_set_friction, rpo_set_mass; their closed forms: tests/test_oracle_params.py) and follows the device step by step with the device's own table rows.  This file
+holds the table and the properties that need no oracle: baked values written back change no bit; an env's values reach that env and no other, in every pipeline and
+through every reset path; a block slides the distance its friction gives; a collision keeps the momentum its masses give.
 """
 import ctypes as C
 import json

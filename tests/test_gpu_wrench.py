@@ -1,7 +1,9 @@
 """Per-env external wrenches (rp_set_wrench / VecPlayEnv.set_wrench, push).  Run with -m gpu on the MI355X box.
 
-The oracle has no external forces, so the feature is held by properties: the table's semantics; a zero table moves no bit in any pipeline; a free
-body in the air follows the substep recurrence the kernel states, in fp64 on the host; an arm link's wrench changes the joint torques by
+Wrenches on bodies in contact - pushed arm links on the furniture, a pushed block between the pads, in all of k_solve2's paths - are held by
+tests/test_gpu_param_lockstep.py: the CPU oracle takes the same wrenches per instance (rpo_set_wrench; its closed forms: tests/test_oracle_params.py) and follows the
+device step by step with the device's own table rows.  This file holds the table and the properties of a body that is alone: the table's semantics; a zero table moves
+no bit in any pipeline; a free body in the air follows the substep recurrence the kernel states, in fp64 on the host; an arm link's wrench changes the joint torques by
 -(J_com^T f + J_w^T t), the Jacobian by central differences of the oracle's forward kinematics; signs on the scene; a wrench in env k reaches env k only;
 set_wrench never waits for the device.
 """
