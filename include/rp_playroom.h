@@ -235,11 +235,15 @@ int rp_render(rp_handle h, const rp_camera* cam, int32_t width, int32_t height, 
               const float* sub_goal, void* stream);
 /* ... with the ghost ARM of visualise_sub_goal(sub_goal, 'controllable_achieved_goal' / 'full_positional_state') (ENV:623-637, 671-674): ghost_arm (may be NULL)
  * [num_envs, 8] = EE position 3, orientation quaternion 4 (xyzw), gripper 1 (unused, as in the reference's reset_arm) - a second arm, half transparent, at the joints one
- * default IK call from the rest pose finds for that pose (ENV:575-590).  Panda models only: RP_ERR_UNSUPPORTED for a UR5 (the reference raises NotImplementedError). */
+ * default IK call from the rest pose finds for that pose (ENV:575-590).  Panda models only: RP_ERR_UNSUPPORTED for a UR5 (the reference raises NotImplementedError).
+ * RP_ERR_ARG (rp_render too): rgb NULL, width or height outside 1 .. 4096, an env range outside the handle's, a camera with a mode other than 0 or 1, fov_deg outside
+ * (0, 180) or aspect <= 0 - and, since both calls draw through rp_render_layers' kernel, num_envs * ceil(width / 16) * ceil(height / 16) > 2^31 - 1 tiles (an rgb buffer
+ * of more than a terabyte; the grid of the kernel they had was an unsigned number of 256-pixel runs and was not checked). */
 int rp_render_ex(rp_handle h, const rp_camera* cam, int32_t width, int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb,
                  const float* sub_goal, const float* ghost_arm, void* stream);
 /* all three layers of getCameraImage (ENV:841-845 takes [2], the colour) for envs [first_env, first_env + num_envs), row 0 = top; each output may be NULL, not all three:
- *   rgb [num_envs, height, width, 3] uint8: byte for byte what rp_render_ex writes for the same arguments (ghosts blended at 0.5, same background, rays 0 .. 10 m).
+ *   rgb [num_envs, height, width, 3] uint8: byte for byte what rp_render_ex writes for the same arguments - by construction: rp_render and rp_render_ex are this call
+ *     with the colour layer alone (ghosts blended at 0.5, rays 0 .. 10 m).
  *   depth [num_envs, height, width] float: the nearest NON-ghost hit of the pixel's ray as eye-space z = t (d . forward), d the normalised ray direction, t the hit
  *     parameter (on a sphere evaluated through the point of closest approach, which does not cancel at a grazing ray as rp_ray_test's float32 quadratic does: the two
  *     differ there by up to some 1e-4 m, elsewhere by rounding).  RP_DEPTH_BUFFER: PyBullet's depthBuffer value far (z - near) / (z (far - near)) clamped to [0, 1]; exactly 1.0 on a miss.  RP_DEPTH_METRES: z itself;
@@ -250,7 +254,7 @@ int rp_render_ex(rp_handle h, const rp_camera* cam, int32_t width, int32_t heigh
  * Cameras: cam as for rp_render (NULL = rp_default_camera; the gripper camera, mode 1, is per env already), OR cam_rows, a DEVICE array [num_envs, 11], row i for env
  * first_env + i: eye[3] target[3] up[3] fov_deg aspect, from which the kernel builds the basis rp_render builds on the host from an rp_camera (same operations, in
  * double, zero-length vectors included).  Never both.  The library does not range-check device values (fov in (0, 180), aspect > 0 are the caller's to keep).
- * RP_ERR_ARG: all three outputs NULL, both cam and cam_rows, near_plane <= 0, far_plane <= near_plane, an unknown depth mode, rp_render_ex's size and range errors.
+ * RP_ERR_ARG: all three outputs NULL, both cam and cam_rows, near_plane <= 0, far_plane <= near_plane, an unknown depth mode, rp_render_ex's size, range and camera errors.
  * RP_ERR_UNSUPPORTED: a ghost arm on a UR5.  Enqueued on `stream`: no host wait, no host read of device values. */
 enum rp_depth_mode { RP_DEPTH_BUFFER = 0, RP_DEPTH_METRES = 1 };
 int rp_render_layers(rp_handle h, const rp_camera* cam, const float* cam_rows /* device [num_envs, 11] or NULL */,

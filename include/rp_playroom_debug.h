@@ -29,8 +29,8 @@ int rp_debug_substep(rp_handle h, int32_t env, float* host_buf);
 int rp_debug_row_counts(rp_handle h, int32_t* host_buf);
 /* the joints [num_envs][8] of the ghost arm(s) drawn by the latest rp_render_ex with a ghost_arm (environments.py:575-590: rest pose, one IK call, joints [0:6]) */
 int rp_debug_ghost_joints(rp_handle h, float* host_buf, int32_t num_envs);
-/* rp_render_layers' tile shortlist: on = 1 (the default) a tile walks only the records whose bounding sphere meets its frustum; on = 0 every record is on every tile's
- * list.  The layers are bit-identical either way (tests/test_gpu_render_layers.py); tools/render_rate.py times one against the other. */
+/* the render kernel's tile shortlist (rp_render, rp_render_ex and rp_render_layers alike: one kernel draws for all three): on = 1 (the default) a tile walks only the
+ * records whose bounding sphere meets its frustum; on = 0 every record is on every tile's list.  The layers are bit-identical either way (tests/test_gpu_render_layers.py); tools/render_rate.py times one against the other. */
 int rp_debug_render_cull(rp_handle h, int32_t on);
 /* rounds the most recent rp_reset took */
 int rp_debug_reset_rounds(rp_handle h);

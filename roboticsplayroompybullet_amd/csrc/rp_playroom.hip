@@ -57,7 +57,7 @@ struct rp_sim {
   float* rs_state; int* rs_idx; int4* rs_meta; int* rs_count; int* rs_sort_cnt; int* rs_sort_slot; int* rs_pair; int* rs_count_host;
   int reset_rounds;        /* rounds the latest rp_reset took (rp_debug) */
   float* rc_tab; int* rc_cnt; float* rc_ee; int rc_cap; int rc_last_num;      /* rp_render / rp_ray_test: collider poses of rc_cap envs (allocated on first use) */
-  int render_nocull;       /* rp_debug_render_cull(h, 0): k_render_layers lists every record for every tile */
+  int render_nocull;       /* rp_debug_render_cull(h, 0): k_render_layers lists every record for every tile (rp_render, rp_render_ex, rp_render_layers) */
   /* rp_step_autoreset: episode counters [N], the list of ending envs [N], its length and take counter [2], k_autoreset's pairing table [4 * ar_grid] */
   int* ep_steps; int* ar_list; int* ar_ctl; int* ar_pair;
   int ar_grid, ar_epb;     /* k_autoreset's grid (the blocks resident at once; RP_AUTORESET_BLOCKS overrides) and envs per block (RP_AUTORESET_EPB, 1 .. 4, default 1) */
@@ -963,27 +963,44 @@ static RpCamera device_camera(const rp_camera* c) {
   return d;
 }
 
-int rp_render_ex(rp_handle h, const rp_camera* cam, int32_t width, int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb,
-                 const float* sub_goal, const float* ghost_arm, void* stream) {
-  if (!h || !rgb || width <= 0 || height <= 0 || width > 4096 || height > 4096 || first_env < 0 || num_envs <= 0 || first_env + num_envs > h->cfg.num_envs) {
-    if (h) snprintf(h->err, 256, "rp_render: bad argument"); return RP_ERR_ARG;
-  }
+/* the one path behind rp_render_ex and rp_render_layers (`who` names the entry point in the messages): the size and range checks, the Panda-only ghost arm, the
+ * tile-count limit, the camera (NULL and no cam_rows = the default one), then k_collider_poses and k_render_layers on `stream` */
+static int render_views(rp_handle h, const char* who, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int metres, int32_t width,
+                        int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb, float* depth, int32_t* segmentation, const float* sub_goal,
+                        const float* ghost_arm, void* stream) {
+  const char* bad = nullptr;
+  if (width <= 0 || height <= 0 || width > 4096 || height > 4096) bad = "bad image size";
+  else if (first_env < 0 || num_envs <= 0 || first_env + num_envs > h->cfg.num_envs) bad = "bad env range";
+  if (bad) { snprintf(h->err, 256, "%s: %s", who, bad); return RP_ERR_ARG; }
   if (ghost_arm && h->host_model.arm_type != RP_ARM_PANDA) {      /* environments.py:629-630: the reference has a ghost arm for the Panda only and raises for the UR5 */
-    snprintf(h->err, 256, "rp_render_ex: the ghost arm exists for the Panda only (environments.py:623-630)"); return RP_ERR_UNSUPPORTED;
+    snprintf(h->err, 256, "%s: the ghost arm exists for the Panda only (environments.py:623-630)", who); return RP_ERR_UNSUPPORTED;
   }
+  const long long blocks = (long long)num_envs * ((width + 15) / 16) * ((height + 15) / 16);
+  if (blocks > 0x7fffffffLL) { snprintf(h->err, 256, "%s: %lld tiles exceed one launch", who, blocks); return RP_ERR_ARG; }
   DevGuard guard(h->cfg.device);
   rp_camera def;
-  if (!cam) { rp_default_camera(&def); cam = &def; }
-  if (cam->mode < 0 || cam->mode > 1 || !(cam->fov_deg > 0.f && cam->fov_deg < 180.f) || !(cam->aspect > 0.f)) { snprintf(h->err, 256, "rp_render: bad camera"); return RP_ERR_ARG; }
+  RpCamera dc; memset(&dc, 0, sizeof(dc));
+  if (!cam_rows) {
+    if (!cam) { rp_default_camera(&def); cam = &def; }
+    if (cam->mode < 0 || cam->mode > 1 || !(cam->fov_deg > 0.f && cam->fov_deg < 180.f) || !(cam->aspect > 0.f)) { snprintf(h->err, 256, "%s: bad camera", who); return RP_ERR_ARG; }
+    dc = device_camera(cam);
+  }
   int rc = rc_reserve(h, num_envs);
   if (rc != RP_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   h->rc_last_num = num_envs;
   hipLaunchKernelGGL(k_collider_poses, dim3(num_envs), dim3(64), 0, s, h->dev_model, h->state, first_env, num_envs, h->rc_tab, h->rc_cnt, sub_goal, h->rc_ee, ghost_arm);
-  const int tiles = (width * height + 255) / 256;
-  hipLaunchKernelGGL(k_render, dim3((unsigned)num_envs * tiles), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, num_envs, device_camera(cam), h->rc_ee, width, height, rgb);
+  hipLaunchKernelGGL(k_render_layers, dim3((unsigned)blocks), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, num_envs, dc, cam_rows, h->rc_ee, width, height,
+                     h->render_nocull ? 0 : 1, near_plane, far_plane, metres, rgb, depth, segmentation);
   HIPCHK(h, hipGetLastError());
   return RP_OK;
+}
+
+int rp_render_ex(rp_handle h, const rp_camera* cam, int32_t width, int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb,
+                 const float* sub_goal, const float* ghost_arm, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  if (!rgb) { snprintf(h->err, 256, "rp_render_ex: no output image (rgb is NULL)"); return RP_ERR_ARG; }
+  return render_views(h, "rp_render_ex", cam, nullptr, 0.01f, 10.f, 0, width, height, first_env, num_envs, rgb, nullptr, nullptr, sub_goal, ghost_arm, stream);      /* (near, far and the mode shape the depth value only) */
 }
 
 int rp_render(rp_handle h, const rp_camera* cam, int32_t width, int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb,
@@ -1001,31 +1018,9 @@ int rp_render_layers(rp_handle h, const rp_camera* cam, const float* cam_rows, f
   else if (!(near_plane > 0.f)) bad = "near_plane <= 0";
   else if (!(far_plane > near_plane)) bad = "far_plane <= near_plane";
   else if (depth_mode != RP_DEPTH_BUFFER && depth_mode != RP_DEPTH_METRES) bad = "unknown depth mode";
-  else if (width <= 0 || height <= 0 || width > 4096 || height > 4096) bad = "bad image size";
-  else if (first_env < 0 || num_envs <= 0 || first_env + num_envs > h->cfg.num_envs) bad = "bad env range";
   if (bad) { snprintf(h->err, 256, "rp_render_layers: %s", bad); return RP_ERR_ARG; }
-  if (ghost_arm && h->host_model.arm_type != RP_ARM_PANDA) {
-    snprintf(h->err, 256, "rp_render_layers: the ghost arm exists for the Panda only (environments.py:623-630)"); return RP_ERR_UNSUPPORTED;
-  }
-  const long long blocks = (long long)num_envs * ((width + 15) / 16) * ((height + 15) / 16);
-  if (blocks > 0x7fffffffLL) { snprintf(h->err, 256, "rp_render_layers: %lld tiles exceed one launch", blocks); return RP_ERR_ARG; }
-  DevGuard guard(h->cfg.device);
-  rp_camera def;
-  RpCamera dc; memset(&dc, 0, sizeof(dc));
-  if (!cam_rows) {
-    if (!cam) { rp_default_camera(&def); cam = &def; }
-    if (cam->mode < 0 || cam->mode > 1 || !(cam->fov_deg > 0.f && cam->fov_deg < 180.f) || !(cam->aspect > 0.f)) { snprintf(h->err, 256, "rp_render_layers: bad camera"); return RP_ERR_ARG; }
-    dc = device_camera(cam);
-  }
-  int rc = rc_reserve(h, num_envs);
-  if (rc != RP_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  h->rc_last_num = num_envs;
-  hipLaunchKernelGGL(k_collider_poses, dim3(num_envs), dim3(64), 0, s, h->dev_model, h->state, first_env, num_envs, h->rc_tab, h->rc_cnt, sub_goal, h->rc_ee, ghost_arm);
-  hipLaunchKernelGGL(k_render_layers, dim3((unsigned)blocks), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, num_envs, dc, cam_rows, h->rc_ee, width, height,
-                     h->render_nocull ? 0 : 1, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, rgb, depth, segmentation);
-  HIPCHK(h, hipGetLastError());
-  return RP_OK;
+  return render_views(h, "rp_render_layers", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, first_env, num_envs, rgb, depth,
+                      segmentation, sub_goal, ghost_arm, stream);
 }
 
 /* test seam and benchmark control: on = 0 puts every record on every tile's shortlist (the default is on) */

@@ -9,8 +9,8 @@
  * second time, half transparent, at the poses a sub-goal vector names.
  *
  *   k_collider_poses   one wave per env: FK -> world pose, half extents, colour of every collider (+ the ghosts of a sub-goal)
- *   k_render           256 pixels per block, the env's collider table staged in LDS, nearest hit per pixel
- *   k_render_layers    a 16 x 16 pixel tile per block, the tile's shortlist of records in LDS: colour, depth and segmentation; per-env cameras (rp_render_layers)
+ *   k_render_layers    a 16 x 16 pixel tile per block, the tile's shortlist of records in LDS, nearest hit per pixel: colour, depth and segmentation; per-env
+ *                      cameras (rp_render, rp_render_ex: the colour alone; rp_render_layers)
  *   k_ray_test         K rays per env against the same table: hit fraction, position, normal, collider, Bullet link index */
 #pragma once
 
@@ -176,12 +176,18 @@ __device__ __forceinline__ bool rc_ray_sphere(const float* rec, V3 o, V3 d, floa
   n_hit = (oc + d * t) * (1.f / r);
   return true;
 }
+/* ... against a collider record, as the shape its type word names: an arm link's hull, a box, a sphere */
+__device__ __forceinline__ bool rc_hit(const DevModel* __restrict__ m, const float* rec, V3 o, V3 d, float tmax, float& t, V3& n) {
+  const int tw = __float_as_int(rec[18]), ci = __float_as_int(rec[19]) & 0xFF;
+  return (tw & RC_HULL) ? rc_ray_hull(rec, (const float4*)m->hpl + m->hpl_off[ci], m->hpl_cnt[ci], o, d, tmax, t, n)
+                        : ((tw & 0xFF) == 0 ? rc_ray_box(rec, o, d, tmax, t, n) : rc_ray_sphere(rec, o, d, tmax, t, n));
+}
 
 /* gripper_camera (environments.py:33-49) from the EE link's rotation R: ori = the link's Euler angles + (0, -pi / 2, 0), rot = the matrix of ori's quaternion, camera
  * vector = rot (1, 0, 0), up vector = rot (0, 0, 1), then computeViewMatrix(pos, pos + camera vector, up vector): f = the camera vector, s = f x up normalised, u = s x f.
  * With (roll, pitch, yaw) the link's angles this is f = Rz(yaw) Ry(pitch) z and u = Rz(yaw) Ry(pitch) (-cos roll, -sin roll, 0) - NOT a fixed rotation of the link frame: it
  * is the link's (-z, +x) only at roll = pi (what rounds 3 to 6 drew for every pose) and (+z, -x) at roll = 0, the reset pose.  The operations are the reference's own, one by
- * one with the library's conversions, so that both render kernels hold the same bits. */
+ * one with the library's conversions; tests/golden/render_parent_checksums.json pins their bits. */
 __device__ __forceinline__ void rc_gripper_basis(const M3& R, V3& fwd, V3& right, V3& up) {
   const Q4 q = m3_to_quat(R);
   const V3 e = euler_from_quat(q.x, q.y, q.z, q.w);
@@ -193,57 +199,8 @@ __device__ __forceinline__ void rc_gripper_basis(const M3& R, V3& fwd, V3& right
   up = cross(right, fwd);
 }
 
-/* obs['img'] (environments.py:841-845): one thread per pixel, row 0 = top of the image, uint8 rgb */
-__global__ void __launch_bounds__(256) k_render(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, int num, RpCamera cam, const float* __restrict__ ee_pose,
-                                                int width, int height, unsigned char* __restrict__ rgb) {
-  __shared__ float T[RC_MAX * RC_STRIDE];
-  const int tiles = (width * height + 255) / 256;
-  const int slot = blockIdx.x / tiles, tile = blockIdx.x - slot * tiles;
-  if (slot >= num) return;
-  const int n = cnt[slot];
-  for (int i = threadIdx.x; i < n * RC_STRIDE; i += 256) T[i] = tab[(size_t)slot * RC_MAX * RC_STRIDE + i];
-  __syncthreads();
-  const int pix = tile * 256 + threadIdx.x;
-  if (pix >= width * height) return;
-  const int px = pix % width, py = pix / width;
-  V3 eye = ld3(cam.eye), fwd = ld3(cam.fwd), right = ld3(cam.right), up = ld3(cam.up);
-  if (cam.mode == 1) {       /* gripper_camera (environments.py:33-49): at the EE link, the reference's basis from the link's Euler angles */
-    const float* e = ee_pose + 12 * slot;
-    eye = ld3(e);
-    rc_gripper_basis(ldm3(e + 3), fwd, right, up);
-  }
-  const float nx = (2.f * (px + 0.5f) / width - 1.f) * cam.tan_half_fov * cam.aspect, ny = (1.f - 2.f * (py + 0.5f) / height) * cam.tan_half_fov;
-  V3 d = fwd + right * nx + up * ny;
-  d = d * (1.f / norm(d));
-  const float far = 10.f;
-  float best = far, gbest = far; V3 bn = mk3(0, 0, 1), gn = bn; int bi = -1, gi = -1;
-  for (int c = 0; c < n; c++) {
-    const float* rec = &T[c * RC_STRIDE];
-    const int tw = __float_as_int(rec[18]);
-    float t; V3 nn;
-    const int ci = __float_as_int(rec[19]) & 0xFF;
-    const bool hit = (tw & RC_HULL) ? rc_ray_hull(rec, (const float4*)m->hpl + m->hpl_off[ci], m->hpl_cnt[ci], eye, d, far, t, nn)
-                                    : ((tw & 0xFF) == 0 ? rc_ray_box(rec, eye, d, far, t, nn) : rc_ray_sphere(rec, eye, d, far, t, nn));
-    if (!hit) continue;
-    if (tw & RC_GHOST) { if (t < gbest) { gbest = t; gn = nn; gi = c; } }
-    else if (t < best) { best = t; bn = nn; bi = c; }
-  }
-  const V3 light = mk3(0.2672612f, -0.5345225f, 0.8017837f);          /* (1, -2, 3) / sqrt(14): fixed directional light */
-  auto shade = [&](int c, V3 nn) {
-    const float* rec = &T[c * RC_STRIDE];
-    const float k = 0.45f + 0.55f * fmaxf(0.f, dot(nn, light));
-    return mk3(rec[15] * k, rec[16] * k, rec[17] * k);
-  };
-  V3 colr = mk3(0.82f, 0.88f, 0.96f);                                    /* background */
-  if (bi >= 0) colr = shade(bi, bn);
-  if (gi >= 0 && gbest < best) colr = colr * 0.5f + shade(gi, gn) * 0.5f;  /* the ghosts are drawn with alpha 0.5 (environments.py:650) */
-  unsigned char* o = rgb + ((size_t)slot * width * height + pix) * 3;
-  o[0] = (unsigned char)(fminf(fmaxf(colr.x, 0.f), 1.f) * 255.f + 0.5f);
-  o[1] = (unsigned char)(fminf(fmaxf(colr.y, 0.f), 1.f) * 255.f + 0.5f);
-  o[2] = (unsigned char)(fminf(fmaxf(colr.z, 0.f), 1.f) * 255.f + 0.5f);
-}
-
-/* rp_render_layers: colour, depth and segmentation of getCameraImage in one pass, a 16 x 16 pixel tile per block.
+/* rp_render, rp_render_ex (obs['img'], environments.py:841-845: the colour alone) and rp_render_layers: colour, depth and segmentation of getCameraImage in one pass, a
+ * 16 x 16 pixel tile per block, one thread per pixel, row 0 = top of the image, uint8 rgb.
  *
  * The block first builds its view (thread 0: the camera's basis - from the launch's RpCamera, from the EE pose for the gripper camera, or from the env's row of
  * cam_rows with device_camera's operations in double) and then the tile's SHORTLIST: one lane per collider record tests the record's bounding sphere (centre p, radius |he|
@@ -251,8 +208,8 @@ __global__ void __launch_bounds__(256) k_render(const DevModel* __restrict__ m, 
  * tile's outermost pixels, whose nx / ny are computed by the very expression the pixels use, so every pixel-centre ray of the tile lies inside it.  A record is dropped only
  * when its sphere lies wholly outside one of the planes by more than a pad of 1e-3 of the distances involved (fp32 rounds at 6e-8; the basis is orthonormal to about 1e-6):
  * then no pixel-centre ray of the tile can meet it, and dropping it cannot change a pixel.  Ballots and a prefix count over the four waves compact the survivors into LDS in
- * ASCENDING record order, so that the lowest record still wins a tie as in k_render.  Each pixel then walks the shortlist with k_render's ray, hit tests and shading
- * (-ffp-contract=off: equal expressions, equal bits).  cull == 0 (rp_debug_render_cull): every record is on every tile's list.
+ * ASCENDING record order, so that the lowest record still wins a tie as it does on the whole table.  Each pixel then walks the shortlist: its ray, rc_hit per record, flat Lambert
+ * shading, the ghosts blended at 0.5.  cull == 0 (rp_debug_render_cull): every record is on every tile's list.
  *
  * depth: the nearest NON-ghost hit as eye-space z = t (d . fwd) - t the hit parameter of the winning record, for a sphere re-evaluated in a well-conditioned form (below; which
  * record wins, and the colour, stay with rc_ray_sphere's t) -; RP_DEPTH_BUFFER far (z - near) / (z (far - near)) clamped to [0, 1], 1 on a miss; RP_DEPTH_METRES z, far on
@@ -288,7 +245,7 @@ __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restric
       V[12] = (float)tan(0.5 * c[9] * 0.01745329251994329547); V[13] = c[10];
     } else {
       V3 eye = ld3(cam.eye), fwd = ld3(cam.fwd), right = ld3(cam.right), up = ld3(cam.up);
-      if (cam.mode == 1) {       /* gripper_camera, as in k_render */
+      if (cam.mode == 1) {       /* gripper_camera (environments.py:33-49): at the EE link, the reference's basis from the link's Euler angles */
         const float* e = ee_pose + 12 * slot;
         eye = ld3(e);
         rc_gripper_basis(ldm3(e + 3), fwd, right, up);
@@ -334,26 +291,22 @@ __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restric
   float best = far, gbest = far; V3 bn = mk3(0, 0, 1), gn = bn; int bi = -1, gi = -1;
   for (int c = 0; c < nl; c++) {
     const float* rec = &T[c * RC_STRIDE];
-    const int tw = __float_as_int(rec[18]);
     float t; V3 nn;
-    const int ci = __float_as_int(rec[19]) & 0xFF;
-    const bool hit = (tw & RC_HULL) ? rc_ray_hull(rec, (const float4*)m->hpl + m->hpl_off[ci], m->hpl_cnt[ci], eye, d, far, t, nn)
-                                    : ((tw & 0xFF) == 0 ? rc_ray_box(rec, eye, d, far, t, nn) : rc_ray_sphere(rec, eye, d, far, t, nn));
-    if (!hit) continue;
-    if (tw & RC_GHOST) { if (t < gbest) { gbest = t; gn = nn; gi = c; } }
+    if (!rc_hit(m, rec, eye, d, far, t, nn)) continue;
+    if (__float_as_int(rec[18]) & RC_GHOST) { if (t < gbest) { gbest = t; gn = nn; gi = c; } }
     else if (t < best) { best = t; bn = nn; bi = c; }
   }
   const size_t pix = (size_t)slot * width * height + (size_t)py * width + px;
   if (rgb) {
-    const V3 light = mk3(0.2672612f, -0.5345225f, 0.8017837f);
+    const V3 light = mk3(0.2672612f, -0.5345225f, 0.8017837f);          /* (1, -2, 3) / sqrt(14): fixed directional light */
     auto shade = [&](int c, V3 nn) {
       const float* rec = &T[c * RC_STRIDE];
       const float k = 0.45f + 0.55f * fmaxf(0.f, dot(nn, light));
       return mk3(rec[15] * k, rec[16] * k, rec[17] * k);
     };
-    V3 colr = mk3(0.82f, 0.88f, 0.96f);
+    V3 colr = mk3(0.82f, 0.88f, 0.96f);                                    /* background */
     if (bi >= 0) colr = shade(bi, bn);
-    if (gi >= 0 && gbest < best) colr = colr * 0.5f + shade(gi, gn) * 0.5f;
+    if (gi >= 0 && gbest < best) colr = colr * 0.5f + shade(gi, gn) * 0.5f;  /* the ghosts are drawn with alpha 0.5 (environments.py:650) */
     unsigned char* o = rgb + pix * 3;
     o[0] = (unsigned char)(fminf(fmaxf(colr.x, 0.f), 1.f) * 255.f + 0.5f);
     o[1] = (unsigned char)(fminf(fmaxf(colr.y, 0.f), 1.f) * 255.f + 0.5f);
@@ -397,13 +350,9 @@ __global__ void __launch_bounds__(64) k_ray_test(const DevModel* __restrict__ m,
     float best = 2.f; V3 bn = mk3(0, 0, 0); int bi = -1;
     for (int c = 0; c < n; c++) {
       const float* rec = &T[c * RC_STRIDE];
-      const int tw = __float_as_int(rec[18]);
-      if (tw & RC_GHOST) continue;
+      if (__float_as_int(rec[18]) & RC_GHOST) continue;
       float t; V3 nn;
-      const int ci = __float_as_int(rec[19]) & 0xFF;
-      const bool hit = (tw & RC_HULL) ? rc_ray_hull(rec, (const float4*)m->hpl + m->hpl_off[ci], m->hpl_cnt[ci], o, d, 1.f, t, nn)
-                                      : ((tw & 0xFF) == 0 ? rc_ray_box(rec, o, d, 1.f, t, nn) : rc_ray_sphere(rec, o, d, 1.f, t, nn));
-      if (hit && t < best) { best = t; bn = nn; bi = c; }            /* the lowest collider index wins ties, as in calc_state's ray */
+      if (rc_hit(m, rec, o, d, 1.f, t, nn) && t < best) { best = t; bn = nn; bi = c; }            /* the lowest collider index wins ties, as in calc_state's ray */
     }
     const bool hit = bi >= 0 && best <= 1.f;
     if (frac) frac[r] = hit ? best : 1.f;

@@ -763,22 +763,27 @@ class VecPlayEnv:
         UR5).  mode 'human' (a GUI window) does not exist here and returns None."""
         if mode == 'human':
             return None
-        lo, hi = (0, self.num_envs) if envs is None else (int(envs[0]), int(envs[1]))
-        n = hi - lo
+        lo, n, sub_goal, ghost_arm = self._render_args(envs, sub_goal, ghost_arm)
         img = out if out is not None else torch.empty((n, int(height), int(width), 3), dtype=torch.uint8, device=self.device)
         assert img.shape == (n, int(height), int(width), 3) and img.dtype == torch.uint8 and img.is_contiguous()
-        sg = None
+        head = (C.byref(camera) if camera is not None else None, int(width), int(height), lo, n, _ptr(img), _ptr(sub_goal))
+        if ghost_arm is not None:
+            self._call('rp_render_ex', *head, _ptr(ghost_arm), self._stream())
+        else:
+            self._call('rp_render', *head, self._stream())
+        return img
+
+    def _render_args(self, envs, sub_goal, ghost_arm):
+        """render's and render_layers': (first env, number of envs, sub_goal, ghost_arm), the two float32, contiguous, on the device and of one row per env (or None)"""
+        lo, hi = (0, self.num_envs) if envs is None else (int(envs[0]), int(envs[1]))
+        n = hi - lo
         if sub_goal is not None:
             sub_goal = sub_goal.to(device=self.device, dtype=torch.float32).contiguous()
             assert sub_goal.shape == (n, self.dims['achieved_goal']), sub_goal.shape
-            sg = _ptr(sub_goal)
         if ghost_arm is not None:
             ghost_arm = ghost_arm.to(device=self.device, dtype=torch.float32).contiguous()
             assert ghost_arm.shape == (n, 8), ghost_arm.shape
-            self._call('rp_render_ex', C.byref(camera) if camera is not None else None, int(width), int(height), lo, n, _ptr(img), sg, _ptr(ghost_arm), self._stream())
-            return img
-        self._call('rp_render', C.byref(camera) if camera is not None else None, int(width), int(height), lo, n, _ptr(img), sg, self._stream())
-        return img
+        return lo, n, sub_goal, ghost_arm
 
     def cameras(self, target=(0.0, 0.25, 0.0), distance=1.3, yaw=-30.0, pitch=-30.0, roll=0.0, fov=50.0, aspect=1.0):
         """per-env cameras for render_layers(cameras=...): the float32 device tensor [n, 11] of camera_rows (each argument a scalar or a length-n host array or
@@ -796,8 +801,8 @@ class VecPlayEnv:
         miss), 'segmentation' int32 [n, height, width] (-1 on a miss, else collider | (link + 1) << 24: unpack_segmentation).  camera: an rp_camera for all envs
         (self.camera(...)), or cameras: a float32 device tensor [n, 11], one row per env (self.cameras(...)) - not both.  Ghosts (sub_goal, ghost_arm: as render's)
         tint rgb only.  out: a dict of preallocated tensors for some or all of the layers.  near / far shape the depth value only.  Nothing is read back."""
-        lo, hi = (0, self.num_envs) if envs is None else (int(envs[0]), int(envs[1]))
-        n, width, height = hi - lo, int(width), int(height)
+        lo, n, sub_goal, ghost_arm = self._render_args(envs, sub_goal, ghost_arm)
+        width, height = int(width), int(height)
         layers = (layers,) if isinstance(layers, str) else tuple(layers)
         shapes = {'rgb': ((n, height, width, 3), torch.uint8), 'depth': ((n, height, width), torch.float32), 'segmentation': ((n, height, width), torch.int32)}
         if not layers or any(k not in shapes for k in layers):
@@ -820,12 +825,6 @@ class VecPlayEnv:
                 t = torch.empty(shape, dtype=dtype, device=self.device)
             assert t.shape == shape and t.dtype == dtype and t.is_contiguous() and t.is_cuda, (k, t.shape, t.dtype)
             res[k] = t
-        if sub_goal is not None:
-            sub_goal = sub_goal.to(device=self.device, dtype=torch.float32).contiguous()
-            assert sub_goal.shape == (n, self.dims['achieved_goal']), sub_goal.shape
-        if ghost_arm is not None:
-            ghost_arm = ghost_arm.to(device=self.device, dtype=torch.float32).contiguous()
-            assert ghost_arm.shape == (n, 8), ghost_arm.shape
         self._call('rp_render_layers', C.byref(camera) if camera is not None else None, _ptr(cameras), float(near), float(far),
                    _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, lo, n, _ptr(res.get('rgb')), _ptr(res.get('depth')),
                    _ptr(res.get('segmentation')), _ptr(sub_goal), _ptr(ghost_arm), self._stream())

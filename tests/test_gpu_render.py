@@ -342,3 +342,19 @@ def test_panda_ghost_arm_of_visualise_sub_goal():
     single.delete_sub_goal()
     assert (single.instance.calc_state()['img'] == before).all()
     single.close()
+
+
+def test_rp_render_bits_of_the_parent(golden):
+    """VecPlayEnv.render (rp_render, rp_render_ex) draws through k_render_layers since the 256-pixel-run kernel it had was retired: every image of
+    tools/render_goldens.py's cases - the cameras and sizes of tests/test_gpu_render_layers.py, after reset() and after five random steps, an env range, the ghosts on
+    the UR5, the Panda and the wide build - keeps the bytes that kernel wrote at the commit the file names.  The state's checksum tells a scene that differs (not this
+    test's subject) from a picture that does."""
+    import render_goldens as g
+    gold = golden('render_parent_checksums.json')
+    assert (gold['steps'], gold['action_seed']) == (g.STEPS, g.ACTION_SEED) and len(gold['commit']) == 40
+    got = g.run()
+    assert [c['case'] for c in got] == gold['cases']
+    for c in got:
+        want = gold['sha256'][c['case']]
+        assert c['state'] == want['state'], '%s: get_state() differs from commit %s: another scene, whatever the picture' % (c['case'], gold['commit'][:7])
+        assert c['image'] == want['image'], '%s: the image differs from the one commit %s drew of the same state' % (c['case'], gold['commit'][:7])

@@ -31,7 +31,7 @@ def test_entry_point_is_declared():
 
 def test_entry_point_is_exported_by_both_libraries_and_mirrored():
     from roboticsplayroompybullet_amd import _lib
-    assert_exported_by_both_libraries(('rp_render_layers',), (b'k_render_layers', b'k_render', b'k_collider_poses'))
+    assert_exported_by_both_libraries(('rp_render_layers',), (b'k_render_layers', b'k_collider_poses'))
     assert 'rp_debug_render_cull' in _lib.DEBUG_EXPORTS and 'rp_debug_render_cull' not in _lib.EXPORTS
     assert (_lib.DEPTH_BUFFER, _lib.DEPTH_METRES) == (0, 1)
     vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
