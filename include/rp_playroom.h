@@ -346,6 +346,26 @@ int rp_set_actuation(rp_handle h, const float* gravity, const float* motor_gain,
 int rp_get_actuation(rp_handle h, float* gravity /* [N, 3] or NULL */, float* motor_gain /* [N, n_arm] or NULL */, float* motor_strength /* [N, n_arm] or NULL */,
                      void* stream);
 
+/* Per-env colours, light and background of the camera images (visual domain randomisation): every env has a float32 device row
+ * vis [N, 3 * n_col + 8] = colour[n_col][3] (rgb in 0 .. 1 of every collider, in collider order: the index rp_ray_test and the segmentation layer report),
+ * light[5] = the direction towards the light dx dy dz (world coordinates, used as it stands: the library does not normalise it), ambient, diffuse, and
+ * background[3], the colour of a pixel whose ray meets nothing.  A hit is drawn as colour * (ambient + diffuse * max(0, n . direction)), n the surface normal.
+ * rp_render, rp_render_ex and rp_render_layers' rgb read the row of env first_env + i for image i, ghosts included (a ghost has its collider's colour); depth,
+ * segmentation and rp_ray_test do not read it.  The button's globe and the dial's grill stay red / white by their state whatever the row says (updateToggles,
+ * ENV:469-483: they show state, not appearance).  The values are parameters, not state: the defaults are the colours of the reference's visual shapes, the light
+ * (1, -2, 3) / sqrt(14) with ambient 0.45 and diffuse 0.55, and the background (0.82, 0.88, 0.96); no reset, rp_set_state or rp_copy_envs changes them and
+ * rp_get_state does not carry them.  With those defaults every image is byte for byte what it is without a table.  The table (up to 800 bytes per env) does not
+ * exist until the first rp_set_visuals or rp_get_visuals, which allocates it and fills it with the defaults on the call's stream; rp_destroy frees it.  Env
+ * indices are the handle's own (0 .. N-1). */
+int rp_get_visuals_dims(rp_handle h, int32_t* n_col);
+/* colour [rows, n_col, 3], light [rows, 5], background [rows, 3], rows = 1 (broadcast) or N, into every env whose mask byte is non-zero (mask NULL = all).
+ * A NULL array leaves that part as it is; all three NULL: RP_ERR_ARG.  rows not 1 or N: RP_ERR_ARG.  Enqueued on `stream`; no host wait, no host read of device
+ * values.  The library does not range-check device values (VecPlayEnv checks host values: colour and background in [0, 1], ambient and diffuse >= 0, a direction
+ * of non-zero length, which it normalises and keeps to seven decimals, so that (1, -2, 3) is the default direction bit for bit). */
+int rp_set_visuals(rp_handle h, const float* colour, const float* light, const float* background, int32_t rows, const uint8_t* mask, void* stream);
+int rp_get_visuals(rp_handle h, float* colour /* [N, n_col, 3] or NULL */, float* light /* [N, 5] or NULL */, float* background /* [N, 3] or NULL */,
+                   void* stream);
+
 /* Per-env joint and body state by column (a drawer half open, a thrown block, an arm at a joint vector without IK; the reference's resetJointState,
  * resetBasePositionAndOrientation, resetBaseVelocity and their getters, ENV:519-603): the kinematic words of the state record as two float32 tables, with
  * n_arm, n_free, n_j1 of rp_get_wrench_dims,
@@ -365,7 +385,7 @@ int rp_set_kinematics(rp_handle h, const float* pos, const float* vel, int32_t r
  * takes the whole state row of env src[e] (int32 [N], device pointer) AS IT WAS BEFORE THE CALL - the state record and, unless RP_CFG_STATELESS_CONTACTS, the
  * contact-cache row: what rp_get_state, a gather of the rows by src and rp_set_state would leave.  Gather semantics: any src is served (permutations, cycles,
  * many-to-one, identity).  With RP_COPY_EPISODE_STEPS the env also takes that env's episode counter.  An env whose src[e] is outside [0, N) is left unchanged.  The
- * dynamics, wrench and actuation tables, the reset table and its cursor are not copied.  Staging: every row is first copied into a buffer of the handle's own, one extra
+ * dynamics, wrench, actuation and visuals tables, the reset table and its cursor are not copied.  Staging: every row is first copied into a buffer of the handle's own, one extra
  * copy of the rows (rp_state_bytes + 4 bytes per env), allocated by the first call and freed by rp_destroy - not the row workspace, so rp_debug_row_counts still sees the
  * latest substep.  Two launches on `stream`; no host wait.  The call reads and writes the state rows and shares the one staging buffer: do not overlap it with rp_step,
  * rp_reset or another rp_copy_envs of the same handle on another stream.  src NULL, unknown flag bits: RP_ERR_ARG. */

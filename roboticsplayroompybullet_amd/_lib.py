@@ -85,7 +85,8 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_last_error', 'rp_version', 'rp_default_camera', 'rp_camera_from_yaw_pitch_roll', 'rp_render', 'rp_render_ex', 'rp_render_layers', 'rp_ray_test',
            'rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset', 'rp_set_reset_table', 'rp_get_reset_rows',
            'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench',
-           'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs']
+           'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs',
+           'rp_get_visuals_dims', 'rp_set_visuals', 'rp_get_visuals']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
                  'rp_debug_autoreset_shape', 'rp_debug_action', 'rp_debug_render_cull']
@@ -135,6 +136,9 @@ def load(wide=False):
     lib.rp_get_actuation_dims.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.rp_set_actuation.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp]
     lib.rp_get_actuation.argtypes = [vp, vp, vp, vp, vp]
+    lib.rp_get_visuals_dims.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.rp_set_visuals.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp]
+    lib.rp_get_visuals.argtypes = [vp, vp, vp, vp, vp]
     lib.rp_get_kinematics.argtypes = [vp, vp, vp, vp]
     lib.rp_set_kinematics.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_uint32, vp]
     lib.rp_copy_envs.argtypes = [vp, vp, vp, C.c_uint32, vp]

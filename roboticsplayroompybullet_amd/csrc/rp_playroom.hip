@@ -63,6 +63,8 @@ struct rp_sim {
   int ar_grid, ar_epb;     /* k_autoreset's grid (the blocks resident at once; RP_AUTORESET_BLOCKS overrides) and envs per block (RP_AUTORESET_EPB, 1 .. 4, default 1) */
   int32_t ar_max_steps; uint32_t ar_when;      /* rp_set_autoreset */
   float* cp_stage;         /* rp_copy_envs: one staged copy of every state row, [N][RP_REC_FLOATS + (PMC_FLOATS)], and behind it the episode counters [N] (allocated at the first call) */
+  float* vis;              /* rp_set_visuals / rp_get_visuals: the per-env visuals table, [N][3 n_col + VIS_TAIL] = colour[n_col][3] light[5] background[3], and behind it the default
+                            * light and background (allocated and filled at the first call; nullptr until then: the render kernels take the baked colours and their literals) */
   /* rp_set_reset_table: the table [rt_rows, rt_n_o] (rt_rows = 0: none), the row cursor [1], each env's row of the latest autoreset step [N] (-1: none), the waves' ballots
    * and first rows [(N + 255) / 256 * 4]; k_autoreset_to's grid (the waves resident at once) */
   float* rt_tab; int rt_rows, rt_n_o; int* rt_cursor; int* rt_env_row; unsigned long long* rt_wave_bal; int* rt_wave_row; int rt_grid;
@@ -148,7 +150,7 @@ static void destroy_handle(rp_sim* h) {        /* frees whatever a (possibly par
   if (!h) return;
   hipFree(h->hullv); hipFree(h->hcv); hipFree(h->hco); hipFree(h->hpl); hipFree(h->pmcache); hipFree(h->dyn); hipFree(h->wrench); hipFree(h->act); hipFree(h->dev_model); hipFree(h->state); hipFree(h->ws); hipFree(h->dbg); hipFree(h->sort_cnt); hipFree(h->sort_slot); hipFree(h->pair_env); hipFree(h->hv_list); hipFree(h->hv_cnt); hipFree(h->member[0]); hipFree(h->member[1]);
   hipFree(h->rc_tab); hipFree(h->rc_cnt); hipFree(h->rc_ee);
-  hipFree(h->ep_steps); hipFree(h->ar_list); hipFree(h->ar_ctl); hipFree(h->ar_pair); hipFree(h->cp_stage);
+  hipFree(h->ep_steps); hipFree(h->ar_list); hipFree(h->ar_ctl); hipFree(h->ar_pair); hipFree(h->cp_stage); hipFree(h->vis);
   hipFree(h->rt_tab); hipFree(h->rt_cursor); hipFree(h->rt_env_row); hipFree(h->rt_wave_bal); hipFree(h->rt_wave_row);
   hipFree(h->rs_state); hipFree(h->rs_idx); hipFree(h->rs_meta); hipFree(h->rs_count); hipFree(h->rs_sort_cnt); hipFree(h->rs_sort_slot); hipFree(h->rs_pair);
   if (h->rs_count_host) hipHostFree(h->rs_count_host);
@@ -841,6 +843,58 @@ int rp_get_kinematics(rp_handle h, float* pos, float* vel, void* stream) {
   return RP_OK;
 }
 
+int rp_get_visuals_dims(rp_handle h, int32_t* n_col) {
+  if (!h || !n_col) return RP_ERR_ARG;
+  *n_col = h->host_model.n_col;
+  return RP_OK;
+}
+
+/* the visuals table at its first use: up to 800 B per env (2.7 GB at the 4 M envs rp_create allows), so a handle that never randomises its image never pays for it.
+ * Allocated here, as rp_copy_envs allocates its staging buffer, and every env's row filled with the default one through launch_table_set on `stream`, ahead of the
+ * caller's set or get: the colours straight from the device model's col_rgb (what k_collider_poses reads without a table), the light and the background - rp_render.cuh's
+ * literals - from eight words behind the table, written on the same stream.  Nothing waits on the host and no device value is read. */
+static int vis_reserve(rp_sim* h, void* stream) {
+  if (h->vis) return RP_OK;
+  const int nc = h->host_model.n_col, W = 3 * nc + VIS_TAIL;
+  const size_t N = (size_t)h->cfg.num_envs;
+  const float tail[VIS_TAIL] = {VIS_LIGHT_X, VIS_LIGHT_Y, VIS_LIGHT_Z, VIS_AMBIENT, VIS_DIFFUSE, VIS_BG_R, VIS_BG_G, VIS_BG_B};
+  float* tab = nullptr;
+  HIPCHK(h, hipMalloc((void**)&tab, (N * W + VIS_TAIL) * sizeof(float)));
+  float* base = tab + N * W;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < VIS_TAIL && e == hipSuccess; k++) {
+    int word;
+    memcpy(&word, &tail[k], sizeof(word));
+    e = hipMemsetD32Async((hipDeviceptr_t)(base + k), word, 1, (hipStream_t)stream);
+  }
+  if (e == hipSuccess) {
+    launch_table_set(h, tab, {&h->dev_model->col_rgb[0][0], base, base + 5, 3 * nc, 5, 3}, 0, 1, nullptr, stream);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) { hipFree(tab); snprintf(h->err, 256, "rp_set_visuals / rp_get_visuals: the table's default rows: %s", hipGetErrorString(e)); return RP_ERR_HIP; }
+  h->vis = tab;
+  return RP_OK;
+}
+
+/* enqueued on `stream` like rp_set_dynamics: a render queued after it on the same stream draws with the new values, one queued before it with the old ones */
+int rp_set_visuals(rp_handle h, const float* colour, const float* light, const float* background, int32_t rows, const uint8_t* mask, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  if (!colour && !light && !background) { snprintf(h->err, 256, "rp_set_visuals: colour, light and background are all NULL"); return RP_ERR_ARG; }
+  if (!rows_ok(h, "rp_set_visuals", rows)) return RP_ERR_ARG;
+  DevGuard guard(h->cfg.device);
+  int rc = vis_reserve(h, stream);
+  if (rc != RP_OK) return rc;
+  return table_set(h, "rp_set_visuals", h->vis, {colour, light, background, 3 * h->host_model.n_col, 5, 3}, 0, rows, mask, stream);
+}
+
+int rp_get_visuals(rp_handle h, float* colour, float* light, float* background, void* stream) {
+  if (!h || (!colour && !light && !background)) { if (h) snprintf(h->err, 256, "rp_get_visuals: colour, light and background are all NULL"); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  int rc = vis_reserve(h, stream);
+  if (rc != RP_OK) return rc;
+  return table_get(h, h->vis, {colour, light, background, 3 * h->host_model.n_col, 5, 3}, stream);
+}
+
 /* two launches on `stream`: every row into the handle's staging buffer, then the masked envs' rows out of it (k_copy_envs_stage / k_copy_envs_gather) */
 int rp_copy_envs(rp_handle h, const int32_t* src, const uint8_t* mask, uint32_t flags, void* stream) {
   if (!h) return RP_ERR_ARG;
@@ -964,7 +1018,8 @@ static RpCamera device_camera(const rp_camera* c) {
 }
 
 /* the one path behind rp_render_ex and rp_render_layers (`who` names the entry point in the messages): the size and range checks, the Panda-only ghost arm, the
- * tile-count limit, the camera (NULL and no cam_rows = the default one), then k_collider_poses and k_render_layers on `stream` */
+ * tile-count limit, the camera (NULL and no cam_rows = the default one), then k_collider_poses and k_render_layers on `stream`, both with the handle's visuals table
+ * (nullptr until the first rp_set_visuals / rp_get_visuals) */
 static int render_views(rp_handle h, const char* who, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int metres, int32_t width,
                         int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb, float* depth, int32_t* segmentation, const float* sub_goal,
                         const float* ghost_arm, void* stream) {
@@ -989,9 +1044,10 @@ static int render_views(rp_handle h, const char* who, const rp_camera* cam, cons
   if (rc != RP_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   h->rc_last_num = num_envs;
-  hipLaunchKernelGGL(k_collider_poses, dim3(num_envs), dim3(64), 0, s, h->dev_model, h->state, first_env, num_envs, h->rc_tab, h->rc_cnt, sub_goal, h->rc_ee, ghost_arm);
+  hipLaunchKernelGGL(k_collider_poses, dim3(num_envs), dim3(64), 0, s, h->dev_model, h->state, first_env, num_envs, h->rc_tab, h->rc_cnt, sub_goal, h->rc_ee, ghost_arm,
+                     (const float*)h->vis);
   hipLaunchKernelGGL(k_render_layers, dim3((unsigned)blocks), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, num_envs, dc, cam_rows, h->rc_ee, width, height,
-                     h->render_nocull ? 0 : 1, near_plane, far_plane, metres, rgb, depth, segmentation);
+                     h->render_nocull ? 0 : 1, near_plane, far_plane, metres, rgb, depth, segmentation, (const float*)h->vis, first_env);
   HIPCHK(h, hipGetLastError());
   return RP_OK;
 }
@@ -1034,7 +1090,8 @@ int rp_ray_test(rp_handle h, const float* from, const float* to, int32_t k, floa
   int rc = rc_reserve(h, N);
   if (rc != RP_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_collider_poses, dim3(N), dim3(64), 0, s, h->dev_model, h->state, 0, N, h->rc_tab, h->rc_cnt, (const float*)nullptr, (float*)nullptr, (const float*)nullptr);
+  hipLaunchKernelGGL(k_collider_poses, dim3(N), dim3(64), 0, s, h->dev_model, h->state, 0, N, h->rc_tab, h->rc_cnt, (const float*)nullptr, (float*)nullptr, (const float*)nullptr,
+                     (const float*)nullptr);      /* (no colour in a ray test's answer) */
   hipLaunchKernelGGL(k_ray_test, dim3(N), dim3(64), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, N, k, from, to, hit_fraction, collider, link, hit_position, hit_normal);
   HIPCHK(h, hipGetLastError());
   return RP_OK;

@@ -8,7 +8,8 @@
  * no textures, no shadows (the reference passes shadow=0).  Sub-goal visualisation (environments.py:606-690) = the same bodies drawn a
  * second time, half transparent, at the poses a sub-goal vector names.
  *
- *   k_collider_poses   one wave per env: FK -> world pose, half extents, colour of every collider (+ the ghosts of a sub-goal)
+ *   k_collider_poses   one wave per env: FK -> world pose, half extents, colour of every collider (+ the ghosts of a sub-goal); the colour from the env's visuals row
+ *                      where rp_set_visuals made a table
  *   k_render_layers    a 16 x 16 pixel tile per block, the tile's shortlist of records in LDS, nearest hit per pixel: colour, depth and segmentation; per-env
  *                      cameras (rp_render, rp_render_ex: the colour alone; rp_render_layers)
  *   k_ray_test         K rays per env against the same table: hit fraction, position, normal, collider, Bullet link index */
@@ -21,14 +22,28 @@
 
 struct RpCamera { float eye[3], fwd[3], right[3], up[3]; float tan_half_fov, aspect; int mode; };   /* mode 1: at the EE link (gripper camera) */
 
+/* per-env visuals (rp_set_visuals): a row of the table is colour[n_col][3], then light = direction towards the light[3] ambient diffuse, then background[3].  The kernels
+ * take a null table as a table of default rows - the baked colours (DevModel.col_rgb) and the literals below - and do the same arithmetic either way */
+#define VIS_TAIL 8            /* floats behind the colours: light 5, background 3 */
+#define VIS_LIGHT_X 0.2672612f
+#define VIS_LIGHT_Y -0.5345225f
+#define VIS_LIGHT_Z 0.8017837f      /* (1, -2, 3) / sqrt(14) */
+#define VIS_AMBIENT 0.45f
+#define VIS_DIFFUSE 0.55f
+#define VIS_BG_R 0.82f
+#define VIS_BG_G 0.88f
+#define VIS_BG_B 0.96f
+
 /* world pose of every collider of env `first + blockIdx.x` into tab[blockIdx.x][RC_MAX][RC_STRIDE]; cnt[blockIdx.x] = records written.
  * sub_goal (may be null): [num][n_ag] achieved-goal vectors to visualise as ghosts (objects, drawer, door, button, dial).
  * ghost_arm (may be null): [num][8] = EE position, orientation quaternion, gripper: the ghost ARM of visualise_sub_goal's 'controllable_achieved_goal' /
  * 'full_positional_state' (environments.py:623-637, 671-674: reset_arm(ghost_arm, sub_goal, from_init=False) = the arm at its rest pose, one default IK call of 20
- * iterations towards the pose, joints [0:6] taken - reset_arm_goal_obs' arithmetic), drawn half transparent like the other ghosts. */
+ * iterations towards the pose, joints [0:6] taken - reset_arm_goal_obs' arithmetic), drawn half transparent like the other ghosts.
+ * vis (may be null): the visuals table [N][3 n_col + VIS_TAIL] of the whole handle; env `first + blockIdx.x` takes its colliders' colours from its own row, ghosts included,
+ * null = the baked colours.  The toggles' red / white (updateToggles) shows state, not appearance, and stands on top of either. */
 __global__ void __launch_bounds__(64) k_collider_poses(const DevModel* __restrict__ m, const float* __restrict__ state, int first, int num,
                                                        float* __restrict__ tab, int* __restrict__ cnt, const float* __restrict__ sub_goal,
-                                                       float* __restrict__ ee_pose, const float* __restrict__ ghost_arm) {
+                                                       float* __restrict__ ee_pose, const float* __restrict__ ghost_arm, const float* __restrict__ vis) {
   __shared__ EnvLds L;
   const int slot = blockIdx.x, lane = threadIdx.x;
   if (slot >= num) return;
@@ -96,7 +111,8 @@ __global__ void __launch_bounds__(64) k_collider_poses(const DevModel* __restric
       for (int k = 0; k < 9; k++) o[k] = x.R.m[k];
       st3(o + 9, x.p);
       st3(o + 12, ld3(m->col_he[lane]));
-      float cr = m->col_rgb[lane][0], cg = m->col_rgb[lane][1], cb = m->col_rgb[lane][2];
+      const float* rgb = vis ? vis + (size_t)env * (3 * m->n_col + VIS_TAIL) + 3 * lane : m->col_rgb[lane];
+      float cr = rgb[0], cg = rgb[1], cb = rgb[2];
       const int tog = m->col_toggle[lane];
       if (tog == 1 && m->n_j1 > 1) { const bool on = L.st[ST_JQ + 1] < 0.025f; cr = 1.f; cg = on ? 0.f : 1.f; cb = on ? 0.f : 1.f; }
       if (tog == 2 && m->n_j1 > 2) { const bool on = dial01(L.st[ST_JQ + 2]) < 0.5f; cr = 1.f; cg = on ? 0.f : 1.f; cb = on ? 0.f : 1.f; }
@@ -213,14 +229,17 @@ __device__ __forceinline__ void rc_gripper_basis(const M3& R, V3& fwd, V3& right
  *
  * depth: the nearest NON-ghost hit as eye-space z = t (d . fwd) - t the hit parameter of the winning record, for a sphere re-evaluated in a well-conditioned form (below; which
  * record wins, and the colour, stay with rc_ray_sphere's t) -; RP_DEPTH_BUFFER far (z - near) / (z (far - near)) clamped to [0, 1], 1 on a miss; RP_DEPTH_METRES z, far on
- * a miss.  seg: collider | (link + 1) << 24 of that hit (rp_ray_test's collider and link), -1 on a miss.  Ghosts tint rgb only. */
+ * a miss.  seg: collider | (link + 1) << 24 of that hit (rp_ray_test's collider and link), -1 on a miss.  Ghosts tint rgb only.
+ *
+ * vis (may be null): the handle's visuals table; thread 0 stages the light and the background of env `first + slot` behind the camera in V[] (null: the literals), and the
+ * shading and the miss colour read them there.  The direction is used as it stands (not normalised).  Depth and segmentation do not read the table. */
 static_assert(RC_MAX <= 256, "k_render_layers: one lane per record");
 __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, int num, RpCamera cam,
                                                        const float* __restrict__ cam_rows, const float* __restrict__ ee_pose, int width, int height, int cull,
                                                        float near_plane, float far_plane, int metres, unsigned char* __restrict__ rgb, float* __restrict__ depth,
-                                                       int* __restrict__ seg) {
+                                                       int* __restrict__ seg, const float* __restrict__ vis, int first) {
   __shared__ float T[RC_MAX * RC_STRIDE];      /* the shortlist's records, compacted */
-  __shared__ float V[14];                      /* eye, fwd, right, up, tan_half_fov, aspect */
+  __shared__ float V[14 + VIS_TAIL];           /* eye, fwd, right, up, tan_half_fov, aspect; light direction, ambient, diffuse, background */
   __shared__ int list[RC_MAX];
   __shared__ int wcnt[4];
   const int tiles_x = (width + 15) >> 4, tiles = tiles_x * ((height + 15) >> 4);
@@ -252,6 +271,13 @@ __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restric
       }
       st3(V, eye); st3(V + 3, fwd); st3(V + 6, right); st3(V + 9, up);
       V[12] = cam.tan_half_fov; V[13] = cam.aspect;
+    }
+    if (vis) {
+      const float* lb = vis + (size_t)(first + slot) * (3 * m->n_col + VIS_TAIL) + 3 * m->n_col;
+      for (int k = 0; k < VIS_TAIL; k++) V[14 + k] = lb[k];
+    } else {
+      V[14] = VIS_LIGHT_X; V[15] = VIS_LIGHT_Y; V[16] = VIS_LIGHT_Z; V[17] = VIS_AMBIENT; V[18] = VIS_DIFFUSE;
+      V[19] = VIS_BG_R; V[20] = VIS_BG_G; V[21] = VIS_BG_B;
     }
   }
   __syncthreads();
@@ -298,13 +324,14 @@ __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restric
   }
   const size_t pix = (size_t)slot * width * height + (size_t)py * width + px;
   if (rgb) {
-    const V3 light = mk3(0.2672612f, -0.5345225f, 0.8017837f);          /* (1, -2, 3) / sqrt(14): fixed directional light */
+    const V3 light = ld3(V + 14);                                         /* the env's directional light (default (1, -2, 3) / sqrt(14)) */
+    const float ambient = V[17], diffuse = V[18];
     auto shade = [&](int c, V3 nn) {
       const float* rec = &T[c * RC_STRIDE];
-      const float k = 0.45f + 0.55f * fmaxf(0.f, dot(nn, light));
+      const float k = ambient + diffuse * fmaxf(0.f, dot(nn, light));
       return mk3(rec[15] * k, rec[16] * k, rec[17] * k);
     };
-    V3 colr = mk3(0.82f, 0.88f, 0.96f);                                    /* background */
+    V3 colr = ld3(V + 19);                                                /* background */
     if (bi >= 0) colr = shade(bi, bn);
     if (gi >= 0 && gbest < best) colr = colr * 0.5f + shade(gi, gn) * 0.5f;  /* the ghosts are drawn with alpha 0.5 (environments.py:650) */
     unsigned char* o = rgb + pix * 3;

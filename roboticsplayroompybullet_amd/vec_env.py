@@ -177,6 +177,40 @@ def check_actuation_values(what, v):
     return _check_values(what, v, *ACTUATION_RANGES[what])
 
 
+@_per_model
+def visual_names(model):
+    """a name per collider of a baked model, in collider order (the index ray_test and the segmentation layer report, the rows of get_visuals' colour): the name
+    dynamics_names(model)['friction'] gives the collider's collision object, so a name repeats where an object has several colliders (the drawer's five boxes)"""
+    objects = dynamics_names(model)['friction']
+    return tuple(objects[c['obj']] for c in _model(model)['col'])
+
+
+VISUAL_WIDTHS = {'colour': 3, 'light': 5, 'background': 3}
+LIGHT_DECIMALS = 7      # decimals a host-side light direction is kept to: those of the default direction's literals (csrc/rp_render.cuh VIS_LIGHT_*)
+
+
+def check_visual_values(what, v):
+    """a host-side colour / light / background value (sequence, numpy array, CPU tensor; the last axis is rgb, or for the light dx dy dz ambient diffuse) as a float32
+    CPU tensor.  Everything finite; colour and background in [0, 1]; ambient and diffuse >= 0; the light's direction of non-zero length, and normalised here, in float64
+    before the float32 cast, because the library uses it as it stands.  The unit vector is kept to seven decimals (LIGHT_DECIMALS), the precision the library's default
+    direction is written in (0.2672612, -0.5345225, 0.8017837): (1, -2, 3) gives that row bit for bit, so writing the documented default draws the default image.  A
+    component is then within 8e-8 of the float64 unit vector (5e-8 from the decimals, 3e-8 from the cast; the cast alone: 3e-8).  ValueError otherwise."""
+    t = torch.as_tensor(v, dtype=torch.float64, device='cpu')
+    if t.dim() == 0 or t.shape[-1] != VISUAL_WIDTHS[what]:
+        raise ValueError('%s: the last axis has %s entries, expected %d' % (what, t.shape[-1] if t.dim() else 'no', VISUAL_WIDTHS[what]))
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError('%s: values must be finite' % what)
+    if what != 'light':
+        return _check_values(what, t, 0.0, 1.0)
+    if not bool((t[..., 3:] >= 0).all()):
+        raise ValueError('light: ambient and diffuse must be >= 0')
+    length = torch.linalg.vector_norm(t[..., :3], dim=-1, keepdim=True)
+    if not bool((length > 0).all()):
+        raise ValueError('light: the direction must have non-zero length')
+    unit = torch.round(t[..., :3] / length * 10.0 ** LIGHT_DECIMALS) / 10.0 ** LIGHT_DECIMALS
+    return _check_values(what, torch.cat([unit, t[..., 3:]], dim=-1))
+
+
 def camera_rows(target=(0.0, 0.25, 0.0), distance=1.3, yaw=-30.0, pitch=-30.0, roll=0.0, fov=50.0, aspect=1.0, n=None):
     """rp_render_layers' cam_rows on the host: a float32 CPU tensor [n, 11] of rows eye[3] target[3] up[3] fov_deg aspect.  Every argument is a scalar or a
     length-n sequence / array / CPU tensor (target: [3] or [n, 3]); n is the longest of them unless given.  Eye and up as rp_camera_from_yaw_pitch_roll computes
@@ -620,6 +654,52 @@ class VecPlayEnv:
         mask = self._mask('set_actuation', mask)
         self._call('rp_set_actuation', *[_ptr(t) for t in parts], rows, _ptr(mask), self._stream())
         self._kept['rp_set_actuation'] = (parts, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
+
+    @property
+    def visual_names(self):
+        """a name per collider, in collider order: the rows of get_visuals' colour (the collider's object as dynamics_names['friction'] calls it; names repeat)"""
+        return visual_names(MODEL_OF[self.env_id])
+
+    def _n_col(self):
+        return self._dims_of('rp_get_visuals_dims', 1)[0]
+
+    def get_visuals(self):
+        """{'colour': [N, n_col, 3], 'light': [N, 5], 'background': [N, 3]} float32 device tensors: every env's rgb per collider (collider order: visual_names), its
+        light (direction towards it dx dy dz, ambient, diffuse) and the colour of a miss (a fresh handle: the reference's colours, (1, -2, 3) / sqrt(14) with 0.45
+        and 0.55, and (0.82, 0.88, 0.96)).  The first get_visuals or set_visuals of a handle allocates the table (up to 800 bytes per env)."""
+        N, nc = self.num_envs, self._n_col()
+        col, light, bg = self._empty(N, nc, 3), self._empty(N, 5), self._empty(N, 3)
+        self._call('rp_get_visuals', _ptr(col), _ptr(light), _ptr(bg), self._stream())
+        return {'colour': col, 'light': light, 'background': bg}
+
+    def set_visuals(self, colour=None, light=None, background=None, mask=None):
+        """Per-env appearance of the camera images: colour per collider ([N, n_col, 3] or [n_col, 3]: every env the same; rgb in 0 .. 1, collider order:
+        visual_names), light ([N, 5] or [5]: direction towards the light, ambient, diffuse - a hit is drawn as colour * (ambient + diffuse * max(0, n . direction)))
+        and background ([N, 3] or [3]: the colour of a miss) for the envs where mask [N] != 0 (None: all); None leaves that part as it is.  render, render_layers'
+        rgb and - since it goes through render - obs['img'] under record_images draw with them from the next call on this stream, ghosts included; depth,
+        segmentation and ray_test do not read them, and the button's globe and the dial's grill keep showing their state in red / white.  No reset, set_state or
+        clone_envs changes them.  Host values (sequences, numpy, CPU tensors) are checked (finite, colours in [0, 1], ambient and diffuse >= 0) and the light's
+        direction is normalised (check_visual_values: (1, -2, 3) is the default direction bit for bit); tensors on the env's device are passed through without a host read and used as they stand, so the call can sit in a device-side
+        loop (e.g. mask=done)."""
+        if colour is None and light is None and background is None:
+            raise ValueError('set_visuals: give colour, light, background or several')
+        parts, rows = self._same_rows([self._block('set_visuals', what, v, shape, lambda x, what=what: check_visual_values(what, x))
+                                       for what, v, shape in (('colour', colour, (self._n_col(), 3)), ('light', light, (5,)), ('background', background, (3,)))])
+        mask = self._mask('set_visuals', mask)
+        self._call('rp_set_visuals', *[_ptr(t) for t in parts], rows, _ptr(mask), self._stream())
+        self._kept['rp_set_visuals'] = (parts, mask)      # (kept until the next set: the kernel reads them when the stream gets there)
+
+    def set_colour(self, name, rgb, mask=None):
+        """Set the colour (3 values, or [N, 3]) of every collider of one object of visual_names for the envs where mask != 0 (None: all), the other colliders'
+        colours untouched: a read-modify-write of the colour table on the device.  An unknown name is a KeyError that lists the names."""
+        names = self.visual_names
+        cols = [c for c, nm in enumerate(names) if nm == name]
+        if not cols:
+            raise KeyError('set_colour: no object %r; the names are %s' % (name, ', '.join(sorted(set(names)))))
+        colour = self.get_visuals()['colour']
+        v = self._block('set_colour', 'rgb', rgb, (3,), lambda x: check_visual_values('colour', x))[0]
+        colour[:, cols, :] = v.reshape(-1, 1, 3)
+        self.set_visuals(colour=colour, mask=mask)
 
     @property
     def kinematics_names(self):

@@ -4,8 +4,10 @@ switched off (rp_debug_render_cull(h, 0)), all three layers with it - at the siz
 200 x 200, UR5PlayAbsRPY1Obj-v0 after 50 random steps.  Every call is k_collider_poses + the render kernel; the 1 x 1 pixel line is what k_collider_poses and the two
 launches cost alone.  Device events around enough back-to-back calls for --window ms per timing, every shape warmed up, three timings per variant and round (their median
 counts), the variants alternated over three rounds; the spread of a variant's own three round medians is the bar a difference has to clear.  To compare two builds, run
-the tool once per build in processes of their own, alternated, with RP_PLAYROOM_LIB naming the library to time.
-usage: python tools/render_rate.py [--out profiles/render_rate_one_kernel.txt] [--window 300] [--n 4096]"""
+the tool once per build in processes of their own, alternated, with RP_PLAYROOM_LIB naming the library to time (a library from before an entry point _lib binds
+cannot be loaded that way: run that commit's own tree).  --visuals random: every handle gets a random per-env visuals table first (rp_set_visuals: colours, light and
+background differ in every env), so the kernels read the table instead of their constants (profiles/visuals_rate.txt); the default, none, never makes the table.
+usage: python tools/render_rate.py [--out profiles/render_rate_one_kernel.txt] [--window 300] [--n 4096] [--visuals none|random]"""
 import argparse
 import os
 import sys
@@ -44,11 +46,24 @@ def stepped_env(n):
     return env
 
 
+def random_visuals(env):
+    """a seeded visuals row per env, built on the device: colours and background uniform in [0, 1), a unit direction in the upper half space, ambient in [0.2, 0.6),
+    diffuse in [0.3, 0.8)"""
+    gen = torch.Generator(device=env.device).manual_seed(5)
+    n = env.num_envs
+    u = lambda *shape: torch.rand(shape, generator=gen, device=env.device)          # noqa: E731
+    d = u(n, 3) * torch.tensor([2.0, 2.0, 1.0], device=env.device) - torch.tensor([1.0, 1.0, -0.2], device=env.device)
+    light = torch.cat([d / d.norm(dim=1, keepdim=True), 0.2 + 0.4 * u(n, 1), 0.3 + 0.5 * u(n, 1)], 1)
+    env.set_visuals(colour=u(n, len(env.visual_names), 3), light=light, background=u(n, 3))
+    torch.cuda.synchronize()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join('profiles', 'render_rate_one_kernel.txt'))
     ap.add_argument('--window', type=float, default=300.0, help='milliseconds of back-to-back calls per timing')
     ap.add_argument('--n', type=int, default=4096)
+    ap.add_argument('--visuals', choices=('none', 'random'), default='none', help='random: a random per-env visuals table is set on every handle first')
     args = ap.parse_args()
     lines = []
 
@@ -59,6 +74,7 @@ def main():
     say('# tools/render_rate.py on %s, one job.  %s after 50 random steps; ms per call = k_collider_poses + the render kernel; device events around >= %d ms of'
         % (torch.cuda.get_device_name(0), GID, args.window))
     say('# back-to-back calls per timing, every shape warmed up, median of three timings per variant and round, variants alternated over three rounds.')
+    say('# visuals: %s' % ('a random table set on every handle (rp_set_visuals)' if args.visuals == 'random' else 'no table (the kernels\' constants)'))
     shapes = [(args.n, 64, 64, False), (args.n, 84, 84, False), (args.n, 84, 84, True), (64, 200, 200, False)]
     env = None
     verdict = []
@@ -67,6 +83,8 @@ def main():
             if env is not None:
                 env.close()
             env = stepped_env(n)
+            if args.visuals == 'random':
+                random_visuals(env)
         cam = env.camera(gripper=True) if gripper else None
         rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=env.device)
         out = {'rgb': rgb, 'depth': torch.empty((n, h, w), dtype=torch.float32, device=env.device),
