@@ -264,6 +264,35 @@ int rp_render_layers(rp_handle h, const rp_camera* cam, const float* cam_rows /*
                      float* depth /* [num_envs, height, width] or NULL */,
                      int32_t* segmentation /* [num_envs, height, width] or NULL */,
                      const float* sub_goal, const float* ghost_arm, void* stream);
+/* ---- camera images written by the calls that write observations ------------------------------------------------------------------------
+ * While set, every call that writes observation rows also draws the images of the same envs, on the call's stream, after the observations and from the state those
+ * observations describe:
+ *   rp_step, rp_calc_state          all envs
+ *   rp_reset, rp_reset_to           the envs of the mask (NULL = all); the rows of unmasked envs are not touched.  rp_reset on RP_ERR_INCOMPLETE too: the image shows
+ *                                   whatever state the row has
+ *   rp_step_autoreset               in the order step, k_autoreset_mark, TERMINAL PASS, the reset kernels, OBSERVATION PASS.  The terminal pass draws, for every env
+ *                                   with done != 0, the layers whose final_* pointer is non-NULL into that env's row of final_*, from the state the step left, before
+ *                                   the reset; rows of envs that did not end are not written.  The observation pass covers all envs: an ended env gets the first frame
+ *                                   of its new episode, as out's observation arrays do.  The step inside the call does not draw on its own: an env is drawn once for
+ *                                   the terminal pass, only if it ended, and once for the observation pass.  All three final_* NULL: no terminal pass.
+ * A row of rgb / depth / segmentation is byte for byte what rp_render_layers(h, cam, cam_rows, near_plane, far_plane, depth_mode, width, height, e, 1, ...) would write
+ * for that env at that moment, without ghosts (sub_goal, ghost_arm = NULL) and with the handle's visuals table (rp_set_visuals); row e of cam_rows belongs to env e.
+ * cam is copied at the call; NULL with no cam_rows = rp_default_camera; mode 1 is the gripper camera, which is per env already.  cam_rows (device [N, 11], rp_render_layers'
+ * layout) is caller-owned, stays referenced until the next rp_set_image_obs and is read on the device at every draw: a caller may rewrite its values between calls (a new
+ * camera for each new episode); the host never reads it.  The output buffers are caller-owned, like the arrays of rp_out: rgb [N, height, width, 3] uint8, depth
+ * [N, height, width] float, segmentation [N, height, width] int32, each may be NULL, not all three; final_* have the same shapes and each may be NULL.
+ * Cost: a stepping call makes two more launches per pass - no host wait, no host read of device values, no allocation; the envs of a pass are selected on the device
+ * (done, mask).  rp_set_image_obs itself reserves the pose table for N envs, and may synchronise the device when it replaces or switches off a configuration that calls
+ * in flight may still read, as rp_set_reset_table does.  width == 0 && height == 0 switches the feature off; the other arguments are then ignored, and the table's memory
+ * stays until rp_destroy.  A handle that never calls this launches exactly what it launched before.
+ * RP_ERR_ARG (the configuration in force stays): rgb, depth and segmentation all NULL while switching on; both cam and cam_rows; rp_render_layers' size, camera,
+ * near / far and depth-mode errors; N * ceil(width / 16) * ceil(height / 16) > 2^31 - 1.
+ * The configuration is not state: rp_get_state, rp_set_state and rp_copy_envs do not carry it.  The image passes share the handle's ONE collider-pose table with
+ * rp_render, rp_render_ex, rp_render_layers and rp_ray_test: do not overlap one of those, or a second call that draws, with a call that draws on another stream. */
+int rp_set_image_obs(rp_handle h, const rp_camera* cam, const float* cam_rows /* device [N, 11] or NULL */,
+                     float near_plane, float far_plane, int32_t depth_mode, int32_t width, int32_t height,
+                     uint8_t* rgb, float* depth, int32_t* segmentation,                      /* [N, h, w, 3] / [N, h, w] / [N, h, w], each may be NULL, not all */
+                     uint8_t* final_rgb, float* final_depth, int32_t* final_segmentation);   /* same shapes, each may be NULL: the ended envs' rows under rp_step_autoreset */
 /* bullet_client.rayTest(from, to) (ENV:738-741) for k rays per env: from / to [N, k, 3] world coordinates.  Outputs (each may be NULL):
  * hit_fraction [N, k] (1 on a miss), collider [N, k] (index into the model's collider table, -1 on a miss), link [N, k] (Bullet link
  * index of an arm collider, -1 otherwise), hit_position [N, k, 3], hit_normal [N, k, 3].  A ray that starts inside a shape does not hit it. */

@@ -86,7 +86,7 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset', 'rp_set_reset_table', 'rp_get_reset_rows',
            'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench',
            'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs',
-           'rp_get_visuals_dims', 'rp_set_visuals', 'rp_get_visuals']
+           'rp_get_visuals_dims', 'rp_set_visuals', 'rp_get_visuals', 'rp_set_image_obs']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
                  'rp_debug_autoreset_shape', 'rp_debug_action', 'rp_debug_render_cull']
@@ -158,6 +158,7 @@ def load(wide=False):
     lib.rp_render.argtypes = [vp, C.POINTER(RpCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
     lib.rp_render_ex.argtypes = [vp, C.POINTER(RpCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.rp_render_layers.argtypes = [vp, C.POINTER(RpCamera), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+    lib.rp_set_image_obs.argtypes = [vp, C.POINTER(RpCamera), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_ray_test.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_debug_substep.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
     lib.rp_set_fused.argtypes = [vp, C.c_int32]

@@ -17,6 +17,14 @@
 #include "rp_render.cuh"
 
 
+/* what one draw needs beyond the envs and the output pointers, checked once (views_check): the device camera, or the caller's device rows, the depth mapping, the image
+ * size and k_render_layers' grid for `num` envs */
+struct RpViews {
+  RpCamera cam; const float* cam_rows;
+  float near_plane, far_plane; int metres;
+  int width, height, num; unsigned blocks;
+};
+
 struct rp_sim {
   rp_config cfg;
   DevModel host_model;
@@ -58,6 +66,9 @@ struct rp_sim {
   int reset_rounds;        /* rounds the latest rp_reset took (rp_debug) */
   float* rc_tab; int* rc_cnt; float* rc_ee; int rc_cap; int rc_last_num;      /* rp_render / rp_ray_test: collider poses of rc_cap envs (allocated on first use) */
   int render_nocull;       /* rp_debug_render_cull(h, 0): k_render_layers lists every record for every tile (rp_render, rp_render_ex, rp_render_layers) */
+  /* rp_set_image_obs: the views of all N envs (io_on = 0: none), the caller's output arrays and the ended envs' (rp_step_autoreset's terminal pass; io_final = any of them) */
+  int io_on, io_final; RpViews io;
+  uint8_t* io_rgb; float* io_depth; int32_t* io_seg; uint8_t* io_frgb; float* io_fdepth; int32_t* io_fseg;
   /* rp_step_autoreset: episode counters [N], the list of ending envs [N], its length and take counter [2], k_autoreset's pairing table [4 * ar_grid] */
   int* ep_steps; int* ar_list; int* ar_ctl; int* ar_pair;
   int ar_grid, ar_epb;     /* k_autoreset's grid (the blocks resident at once; RP_AUTORESET_BLOCKS overrides) and envs per block (RP_AUTORESET_EPB, 1 .. 4, default 1) */
@@ -123,6 +134,8 @@ static int table_get(rp_sim* h, const float* tab, TabCols<float> c, void* stream
   HIPCHK(h, hipGetLastError());
   return RP_OK;
 }
+
+static void image_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s);      /* (beside the render entry points, below) */
 
 static OutPtrs to_ptrs(const rp_out* o) {
   OutPtrs p;
@@ -501,10 +514,12 @@ static int reset_impl(rp_handle h, const float* o, int32_t n_o, const uint8_t* m
   hipLaunchKernelGGL(k_episode_zero, dim3((N + 255) / 256), dim3(256), 0, s, mask, h->ep_steps, N);      /* the reset envs start a new episode */
   if (!o && h->fused != 1) {
     int rc = reset_split(h, mask, out, s);
+    if (rc == RP_ERR_INCOMPLETE) image_pass(h, false, nullptr, mask, s);      /* (the rows are written, pending envs included: the images show the state they have) */
     if (rc != RP_OK) return rc;
   } else {          /* reset(o) has no settle phase; the fused path keeps everything in one kernel */
     hipLaunchKernelGGL(k_reset, dim3(N), dim3(64), 0, s, h->dev_model, h->state, mask, to_ptrs(out), N, h->cfg.seed, (uint32_t)h->cfg.env_offset, o, (int)n_o);
   }
+  image_pass(h, false, nullptr, mask, s);      /* rp_set_image_obs: the images of the envs whose rows were written */
   HIPCHK(h, hipGetLastError());
   if (h->timers_on) { hipEventRecord(h->ev1, s); hipEventSynchronize(h->ev1); hipEventElapsedTime(&h->timers.last_reset_ms, h->ev0, h->ev1); }
   return RP_OK;
@@ -557,7 +572,8 @@ static GroupBounds split_groups(rp_handle h, int G, int N) {
   return gb;
 }
 
-int rp_step(rp_handle h, const float* action, const rp_out* out, void* stream) {
+/* rp_step without the image observations: rp_step_autoreset draws its own, around the resets */
+static int step_impl(rp_handle h, const float* action, const rp_out* out, void* stream) {
   if (!h || !action) { if (h) snprintf(h->err, 256, "rp_step: action is NULL"); return RP_ERR_ARG; }
   DevGuard guard(h->cfg.device);
   hipStream_t s = (hipStream_t)stream;
@@ -689,6 +705,15 @@ int rp_step(rp_handle h, const float* action, const rp_out* out, void* stream) {
   return RP_OK;
 }
 
+int rp_step(rp_handle h, const float* action, const rp_out* out, void* stream) {
+  int rc = step_impl(h, action, out, stream);
+  if (rc != RP_OK || !h->io_on) return rc;
+  DevGuard guard(h->cfg.device);
+  image_pass(h, false, nullptr, nullptr, (hipStream_t)stream);      /* on the caller's stream, which the group streams have joined */
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
 int rp_set_autoreset(rp_handle h, int32_t max_episode_steps, uint32_t when) {
   if (!h) return RP_ERR_ARG;
   if (when & ~(uint32_t)(RP_AR_TIME_LIMIT | RP_AR_FAULT | RP_AR_SUCCESS)) { snprintf(h->err, 256, "rp_set_autoreset: unknown bits in when (0x%x)", when); return RP_ERR_ARG; }
@@ -711,12 +736,13 @@ int rp_set_episode_steps(rp_handle h, const int32_t* src, void* stream) {
 }
 
 /* rp_step, then on the same stream: k_autoreset_mark (done bits, final_out rows, counters, the list of ending envs) and ONE k_autoreset launch that resets the listed envs
- * (an empty list: its blocks leave at once).  Nothing is read back; the call returns when everything is enqueued. */
+ * (an empty list: its blocks leave at once).  Nothing is read back; the call returns when everything is enqueued.  With rp_set_image_obs: the step does not draw; the
+ * terminal pass (the envs with done != 0, by the kernels' selection: their blocks alone do work) stands between the mark and the reset, the observation pass at the end. */
 int rp_step_autoreset(rp_handle h, const float* action, const uint8_t* end_mask, const rp_out* out, const rp_out* final_out, int32_t* done, void* stream) {
   if (!h || !action || !done) { if (h) snprintf(h->err, 256, "rp_step_autoreset: action or done is NULL"); return RP_ERR_ARG; }
   if ((h->ar_when & RP_AR_FAULT) && (!out || !out->status)) { snprintf(h->err, 256, "rp_step_autoreset: RP_AR_FAULT reads out.status, which is NULL"); return RP_ERR_ARG; }
   if ((h->ar_when & RP_AR_SUCCESS) && (!out || !out->is_success)) { snprintf(h->err, 256, "rp_step_autoreset: RP_AR_SUCCESS reads out.is_success, which is NULL"); return RP_ERR_ARG; }
-  int rc = rp_step(h, action, out, stream);
+  int rc = step_impl(h, action, out, stream);
   if (rc != RP_OK) return rc;
   DevGuard guard(h->cfg.device);
   hipStream_t s = (hipStream_t)stream;
@@ -726,6 +752,7 @@ int rp_step_autoreset(rp_handle h, const float* action, const uint8_t* end_mask,
   const bool table = h->rt_rows > 0;
   hipLaunchKernelGGL(k_autoreset_mark, dim3((N + 255) / 256), dim3(256), 0, s, h->dev_model, N, (int)h->ar_max_steps, (unsigned)h->ar_when, end_mask, op, fp, done, h->ep_steps,
                      h->ar_list, h->ar_ctl, h->rt_env_row, table ? h->rt_wave_bal : (unsigned long long*)nullptr);
+  image_pass(h, true, done, nullptr, s);       /* rp_set_image_obs' terminal pass: the ended envs' last frame, from the state the step left, into final_* */
   if (table) {
     hipLaunchKernelGGL(k_autoreset_rows, dim3(1), dim3(1024), 0, s, (const unsigned long long*)h->rt_wave_bal, (N + 63) / 64, h->rt_wave_row, h->rt_cursor, h->rt_rows);
     hipLaunchKernelGGL(k_autoreset_to, dim3(h->rt_grid), dim3(64), 0, s, h->dev_model, h->state, (const int*)h->ar_list, (const int*)h->ar_ctl,
@@ -735,6 +762,7 @@ int rp_step_autoreset(rp_handle h, const float* action, const uint8_t* end_mask,
     hipLaunchKernelGGL(k_autoreset, dim3(h->ar_grid), dim3(64 * SOLVE_WAVES), 0, s, h->dev_model, h->state, h->ws, (const int*)h->ar_list, h->ar_ctl, h->ar_pair, op, h->cfg.seed,
                        (uint32_t)h->cfg.env_offset, h->ar_epb, h->debug_flags);
   }
+  image_pass(h, false, nullptr, nullptr, s);   /* ... and its observation pass: every env, the ended ones at their new episode's first frame */
   HIPCHK(h, hipGetLastError());
   return RP_OK;
 }
@@ -927,6 +955,7 @@ int rp_calc_state(rp_handle h, const rp_out* out, void* stream) {
   DevGuard guard(h->cfg.device);
   int N = h->cfg.num_envs;
   hipLaunchKernelGGL(k_calc_state, dim3(N), dim3(64), 0, (hipStream_t)stream, h->dev_model, h->state, to_ptrs(out), 0, N, (const int*)nullptr);
+  image_pass(h, false, nullptr, nullptr, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return RP_OK;
 }
@@ -1017,12 +1046,10 @@ static RpCamera device_camera(const rp_camera* c) {
   return d;
 }
 
-/* the one path behind rp_render_ex and rp_render_layers (`who` names the entry point in the messages): the size and range checks, the Panda-only ghost arm, the
- * tile-count limit, the camera (NULL and no cam_rows = the default one), then k_collider_poses and k_render_layers on `stream`, both with the handle's visuals table
- * (nullptr until the first rp_set_visuals / rp_get_visuals) */
-static int render_views(rp_handle h, const char* who, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int metres, int32_t width,
-                        int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb, float* depth, int32_t* segmentation, const float* sub_goal,
-                        const float* ghost_arm, void* stream) {
+/* the checks of a draw (`who` names the entry point in the messages): the size and range checks, the Panda-only ghost arm, the tile-count limit, the camera (NULL and
+ * no cam_rows = the default one); *v is what views_launch needs.  Touches no device. */
+static int views_check(rp_handle h, const char* who, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int metres, int32_t width,
+                       int32_t height, int32_t first_env, int32_t num_envs, const float* ghost_arm, RpViews* v) {
   const char* bad = nullptr;
   if (width <= 0 || height <= 0 || width > 4096 || height > 4096) bad = "bad image size";
   else if (first_env < 0 || num_envs <= 0 || first_env + num_envs > h->cfg.num_envs) bad = "bad env range";
@@ -1032,23 +1059,91 @@ static int render_views(rp_handle h, const char* who, const rp_camera* cam, cons
   }
   const long long blocks = (long long)num_envs * ((width + 15) / 16) * ((height + 15) / 16);
   if (blocks > 0x7fffffffLL) { snprintf(h->err, 256, "%s: %lld tiles exceed one launch", who, blocks); return RP_ERR_ARG; }
-  DevGuard guard(h->cfg.device);
   rp_camera def;
-  RpCamera dc; memset(&dc, 0, sizeof(dc));
+  memset(v, 0, sizeof(*v));
   if (!cam_rows) {
     if (!cam) { rp_default_camera(&def); cam = &def; }
     if (cam->mode < 0 || cam->mode > 1 || !(cam->fov_deg > 0.f && cam->fov_deg < 180.f) || !(cam->aspect > 0.f)) { snprintf(h->err, 256, "%s: bad camera", who); return RP_ERR_ARG; }
-    dc = device_camera(cam);
+    v->cam = device_camera(cam);
   }
-  int rc = rc_reserve(h, num_envs);
+  v->cam_rows = cam_rows; v->near_plane = near_plane; v->far_plane = far_plane; v->metres = metres;
+  v->width = width; v->height = height; v->num = num_envs; v->blocks = (unsigned)blocks;
+  return RP_OK;
+}
+
+/* k_collider_poses and k_render_layers for envs [first_env, first_env + v.num) on `s`, both with the handle's visuals table (nullptr until the first rp_set_visuals /
+ * rp_get_visuals) and the selection sel32 / sel8 (rc_selected; indexed by env, so a selection goes with first_env = 0).  The pose table holds v.num envs (rc_reserve). */
+static void views_launch(rp_handle h, const RpViews& v, int first_env, uint8_t* rgb, float* depth, int32_t* segmentation, const float* sub_goal, const float* ghost_arm,
+                         const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
+  const bool sel = sel32 || sel8;      /* the kernels' SEL = true instantiations only where there is a selection: without one they are the kernels they were */
+  hipLaunchKernelGGL(sel ? k_collider_poses<true> : k_collider_poses<false>, dim3(v.num), dim3(64), 0, s, h->dev_model, h->state, first_env, v.num, h->rc_tab, h->rc_cnt,
+                     sub_goal, h->rc_ee, ghost_arm, (const float*)h->vis, (const int*)sel32, sel8);
+  hipLaunchKernelGGL(sel ? k_render_layers<true> : k_render_layers<false>, dim3(v.blocks), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, v.num, v.cam, v.cam_rows,
+                     h->rc_ee, v.width, v.height, h->render_nocull ? 0 : 1, v.near_plane, v.far_plane, v.metres, rgb, depth, segmentation, (const float*)h->vis, first_env,
+                     (const int*)sel32, sel8);
+}
+
+/* rp_set_image_obs' draw inside a call that writes observation rows: all N envs, or those sel32 / sel8 select on the device, into the observation arrays (final = false)
+ * or the ended envs' (final = true: rp_step_autoreset's terminal pass).  Two launches on `s`; nothing is checked, reserved or read back here. */
+static void image_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
+  if (!h->io_on || (final && !h->io_final)) return;
+  if (final) views_launch(h, h->io, 0, h->io_frgb, h->io_fdepth, h->io_fseg, nullptr, nullptr, sel32, sel8, s);
+  else views_launch(h, h->io, 0, h->io_rgb, h->io_depth, h->io_seg, nullptr, nullptr, sel32, sel8, s);
+}
+
+/* the one path behind rp_render_ex and rp_render_layers: views_check, the pose table for the call's envs, views_launch on `stream` */
+static int render_views(rp_handle h, const char* who, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int metres, int32_t width,
+                        int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb, float* depth, int32_t* segmentation, const float* sub_goal,
+                        const float* ghost_arm, void* stream) {
+  RpViews v;
+  int rc = views_check(h, who, cam, cam_rows, near_plane, far_plane, metres, width, height, first_env, num_envs, ghost_arm, &v);
   if (rc != RP_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
+  DevGuard guard(h->cfg.device);
+  rc = rc_reserve(h, num_envs);
+  if (rc != RP_OK) return rc;
   h->rc_last_num = num_envs;
-  hipLaunchKernelGGL(k_collider_poses, dim3(num_envs), dim3(64), 0, s, h->dev_model, h->state, first_env, num_envs, h->rc_tab, h->rc_cnt, sub_goal, h->rc_ee, ghost_arm,
-                     (const float*)h->vis);
-  hipLaunchKernelGGL(k_render_layers, dim3((unsigned)blocks), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, num_envs, dc, cam_rows, h->rc_ee, width, height,
-                     h->render_nocull ? 0 : 1, near_plane, far_plane, metres, rgb, depth, segmentation, (const float*)h->vis, first_env);
+  views_launch(h, v, first_env, rgb, depth, segmentation, sub_goal, ghost_arm, nullptr, nullptr, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+/* rp_render_layers' own argument rules, which rp_set_image_obs shares: the complaint, or null */
+static const char* layers_complaint(const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int32_t depth_mode, const void* rgb, const void* depth,
+                                    const void* segmentation) {
+  if (!rgb && !depth && !segmentation) return "no output layer (rgb, depth and segmentation are all NULL)";
+  if (cam && cam_rows) return "both cam and cam_rows given";
+  if (!(near_plane > 0.f)) return "near_plane <= 0";
+  if (!(far_plane > near_plane)) return "far_plane <= near_plane";
+  if (depth_mode != RP_DEPTH_BUFFER && depth_mode != RP_DEPTH_METRES) return "unknown depth mode";
+  return nullptr;
+}
+
+/* The image observations: every check is made here, once, and the stepping calls only launch (image_pass).  The pose table is reserved for all N envs here, so that no
+ * stepping call allocates; where that replaces a smaller table, hipFree waits for the device, and so does this call before it replaces a configuration that calls in
+ * flight on other streams were launched with (their kernels hold the old pointers; the caller may free those buffers once this call has returned). */
+int rp_set_image_obs(rp_handle h, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int32_t depth_mode, int32_t width, int32_t height,
+                     uint8_t* rgb, float* depth, int32_t* segmentation, uint8_t* final_rgb, float* final_depth, int32_t* final_segmentation) {
+  if (!h) return RP_ERR_ARG;
+  DevGuard guard(h->cfg.device);
+  if (width == 0 && height == 0) {
+    if (h->io_on) HIPCHK(h, hipDeviceSynchronize());
+    h->io_on = 0; h->io_final = 0;
+    return RP_OK;
+  }
+  const char* bad = layers_complaint(cam, cam_rows, near_plane, far_plane, depth_mode, rgb, depth, segmentation);
+  if (bad) { snprintf(h->err, 256, "rp_set_image_obs: %s", bad); return RP_ERR_ARG; }
+  RpViews v;
+  int rc = views_check(h, "rp_set_image_obs", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, 0, h->cfg.num_envs, nullptr, &v);
+  if (rc != RP_OK) return rc;
+  if (h->io_on) HIPCHK(h, hipDeviceSynchronize());
+  rc = rc_reserve(h, h->cfg.num_envs);
+  if (rc != RP_OK) { h->io_on = 0; h->io_final = 0; return rc; }      /* (the table it had may be gone) */
+  h->io = v;
+  h->io_rgb = rgb; h->io_depth = depth; h->io_seg = segmentation;
+  /* a terminal layer without its observation layer is drawn all the same: the final_* pointers stand for themselves */
+  h->io_frgb = final_rgb; h->io_fdepth = final_depth; h->io_fseg = final_segmentation;
+  h->io_final = (final_rgb || final_depth || final_segmentation) ? 1 : 0;
+  h->io_on = 1;
   return RP_OK;
 }
 
@@ -1068,12 +1163,7 @@ int rp_render_layers(rp_handle h, const rp_camera* cam, const float* cam_rows, f
                      int32_t width, int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb, float* depth, int32_t* segmentation,
                      const float* sub_goal, const float* ghost_arm, void* stream) {
   if (!h) return RP_ERR_ARG;
-  const char* bad = nullptr;
-  if (!rgb && !depth && !segmentation) bad = "no output layer (rgb, depth and segmentation are all NULL)";
-  else if (cam && cam_rows) bad = "both cam and cam_rows given";
-  else if (!(near_plane > 0.f)) bad = "near_plane <= 0";
-  else if (!(far_plane > near_plane)) bad = "far_plane <= near_plane";
-  else if (depth_mode != RP_DEPTH_BUFFER && depth_mode != RP_DEPTH_METRES) bad = "unknown depth mode";
+  const char* bad = layers_complaint(cam, cam_rows, near_plane, far_plane, depth_mode, rgb, depth, segmentation);
   if (bad) { snprintf(h->err, 256, "rp_render_layers: %s", bad); return RP_ERR_ARG; }
   return render_views(h, "rp_render_layers", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, first_env, num_envs, rgb, depth,
                       segmentation, sub_goal, ghost_arm, stream);
@@ -1090,8 +1180,8 @@ int rp_ray_test(rp_handle h, const float* from, const float* to, int32_t k, floa
   int rc = rc_reserve(h, N);
   if (rc != RP_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_collider_poses, dim3(N), dim3(64), 0, s, h->dev_model, h->state, 0, N, h->rc_tab, h->rc_cnt, (const float*)nullptr, (float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr);      /* (no colour in a ray test's answer) */
+  hipLaunchKernelGGL(k_collider_poses<false>, dim3(N), dim3(64), 0, s, h->dev_model, h->state, 0, N, h->rc_tab, h->rc_cnt, (const float*)nullptr, (float*)nullptr, (const float*)nullptr,
+                     (const float*)nullptr, (const int*)nullptr, (const unsigned char*)nullptr);      /* (no colour in a ray test's answer) */
   hipLaunchKernelGGL(k_ray_test, dim3(N), dim3(64), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, N, k, from, to, hit_fraction, collider, link, hit_position, hit_normal);
   HIPCHK(h, hipGetLastError());
   return RP_OK;

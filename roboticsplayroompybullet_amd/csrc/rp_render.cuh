@@ -12,6 +12,7 @@
  *                      where rp_set_visuals made a table
  *   k_render_layers    a 16 x 16 pixel tile per block, the tile's shortlist of records in LDS, nearest hit per pixel: colour, depth and segmentation; per-env
  *                      cameras (rp_render, rp_render_ex: the colour alone; rp_render_layers)
+ *                      both as <SEL = true> too: the envs a device array selects (rp_set_image_obs: the ended envs' terminal frames, a masked reset's images)
  *   k_ray_test         K rays per env against the same table: hit fraction, position, normal, collider, Bullet link index */
 #pragma once
 
@@ -34,20 +35,33 @@ struct RpCamera { float eye[3], fwd[3], right[3], up[3]; float tan_half_fov, asp
 #define VIS_BG_G 0.88f
 #define VIS_BG_B 0.96f
 
+/* a subset of the envs that the DEVICE names (rp_set_image_obs: rp_step_autoreset's done[N] for the terminal frames, a reset's mask[N]): env is drawn unless its word of
+ * sel32 or its byte of sel8 is 0; both indexed by env, each may be null.  The two kernels that take a selection are templates on SEL: SEL = false never looks at the
+ * pointers and is, instruction for instruction, the kernel without a selection (with the test compiled in and null pointers the compiler laid out the ray loop's branches
+ * another way, and a draw of all envs cost 0.5 % more: profiles/image_obs_rate.txt); the host launches SEL = true only where a pointer is given. */
+__device__ __forceinline__ bool rc_selected(const int* __restrict__ sel32, const unsigned char* __restrict__ sel8, int env) {
+  return !(sel32 && sel32[env] == 0) && !(sel8 && sel8[env] == 0);
+}
+
 /* world pose of every collider of env `first + blockIdx.x` into tab[blockIdx.x][RC_MAX][RC_STRIDE]; cnt[blockIdx.x] = records written.
  * sub_goal (may be null): [num][n_ag] achieved-goal vectors to visualise as ghosts (objects, drawer, door, button, dial).
  * ghost_arm (may be null): [num][8] = EE position, orientation quaternion, gripper: the ghost ARM of visualise_sub_goal's 'controllable_achieved_goal' /
  * 'full_positional_state' (environments.py:623-637, 671-674: reset_arm(ghost_arm, sub_goal, from_init=False) = the arm at its rest pose, one default IK call of 20
  * iterations towards the pose, joints [0:6] taken - reset_arm_goal_obs' arithmetic), drawn half transparent like the other ghosts.
  * vis (may be null): the visuals table [N][3 n_col + VIS_TAIL] of the whole handle; env `first + blockIdx.x` takes its colliders' colours from its own row, ghosts included,
- * null = the baked colours.  The toggles' red / white (updateToggles) shows state, not appearance, and stands on top of either. */
+ * null = the baked colours.  The toggles' red / white (updateToggles) shows state, not appearance, and stands on top of either.
+ * sel32, sel8 (each may be null): the selection (rc_selected); the block of an unselected env leaves at the top, before the state load and any barrier, and writes
+ * nothing: its slot of tab / cnt / ee_pose keeps what it held. */
+template <bool SEL>
 __global__ void __launch_bounds__(64) k_collider_poses(const DevModel* __restrict__ m, const float* __restrict__ state, int first, int num,
                                                        float* __restrict__ tab, int* __restrict__ cnt, const float* __restrict__ sub_goal,
-                                                       float* __restrict__ ee_pose, const float* __restrict__ ghost_arm, const float* __restrict__ vis) {
+                                                       float* __restrict__ ee_pose, const float* __restrict__ ghost_arm, const float* __restrict__ vis,
+                                                       const int* __restrict__ sel32, const unsigned char* __restrict__ sel8) {
   __shared__ EnvLds L;
   const int slot = blockIdx.x, lane = threadIdx.x;
   if (slot >= num) return;
   const int env = first + slot;
+  if (SEL && !rc_selected(sel32, sel8, env)) return;      /* block-uniform: the whole wave leaves */
   load_state(L, state, env, lane);
   float* out = tab + (size_t)slot * RC_MAX * RC_STRIDE;
   const bool obj_ghosts = sub_goal && m->num_objects > 0;
@@ -232,12 +246,17 @@ __device__ __forceinline__ void rc_gripper_basis(const M3& R, V3& fwd, V3& right
  * a miss.  seg: collider | (link + 1) << 24 of that hit (rp_ray_test's collider and link), -1 on a miss.  Ghosts tint rgb only.
  *
  * vis (may be null): the handle's visuals table; thread 0 stages the light and the background of env `first + slot` behind the camera in V[] (null: the literals), and the
- * shading and the miss colour read them there.  The direction is used as it stands (not normalised).  Depth and segmentation do not read the table. */
+ * shading and the miss colour read them there.  The direction is used as it stands (not normalised).  Depth and segmentation do not read the table.
+ *
+ * sel32, sel8 (each may be null): k_collider_poses' selection, by env `first + slot`; every tile's block of an unselected env leaves before the view is built - all 256
+ * threads, ahead of the first barrier - and the env's rows of rgb / depth / seg keep what they held. */
 static_assert(RC_MAX <= 256, "k_render_layers: one lane per record");
+template <bool SEL>
 __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, int num, RpCamera cam,
                                                        const float* __restrict__ cam_rows, const float* __restrict__ ee_pose, int width, int height, int cull,
                                                        float near_plane, float far_plane, int metres, unsigned char* __restrict__ rgb, float* __restrict__ depth,
-                                                       int* __restrict__ seg, const float* __restrict__ vis, int first) {
+                                                       int* __restrict__ seg, const float* __restrict__ vis, int first, const int* __restrict__ sel32,
+                                                       const unsigned char* __restrict__ sel8) {
   __shared__ float T[RC_MAX * RC_STRIDE];      /* the shortlist's records, compacted */
   __shared__ float V[14 + VIS_TAIL];           /* eye, fwd, right, up, tan_half_fov, aspect; light direction, ambient, diffuse, background */
   __shared__ int list[RC_MAX];
@@ -247,6 +266,7 @@ __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restric
    * eight (64 x 64: 16), the few tiles that hold the arm - whose hulls cost a ray hundreds of plane tests - would always land on the same XCDs */
   const int tile = blockIdx.x / num, slot = blockIdx.x - tile * num;
   if (tile >= tiles) return;
+  if (SEL && !rc_selected(sel32, sel8, first + slot)) return;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) {

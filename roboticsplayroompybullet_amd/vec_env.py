@@ -346,6 +346,9 @@ class VecPlayEnv:
         self._img = None                    # reused image buffer: obs['img'] is overwritten by the next step / reset / calc_state (clone() to keep one)
         self.sub_goal = None                # [N, dims.achieved_goal] ghosts drawn into img (visualise_sub_goal)
         self.ghost_arm = None               # [N, 8] ghost arm poses drawn into img (visualise_sub_goal's arm part, Panda ids)
+        self.image_obs = None               # set_image_obs: {'rgb' / 'depth' / 'segmentation': the tensors step / reset / calc_state write}, owned like buf
+        self.image_final = None             # ... and under autoreset the ended envs' last frames (info['terminal_observation'])
+        self.image_cameras = None           # ... and its per-env cameras [N, 11], read on the device at every draw: rewrite rows in place
         self.autoreset = bool(autoreset)
         if self.autoreset:
             limit = self._max_episode_steps if max_episode_steps is None else int(max_episode_steps)
@@ -376,7 +379,9 @@ class VecPlayEnv:
         o = {k: self.buf[k] for k in OBS_KEYS}
         # environments.py:841-845: img only while record_images is set (render('rgb_array')); all envs, [N, 200, 200, 3] uint8
         o['img'] = None
-        if self.record_images:
+        if self.image_obs is not None:      # set_image_obs: the library drew them inside the call that wrote buf
+            o.update(self._image_keys(self.image_obs))
+        elif self.record_images:
             lo, hi = self.image_envs or (0, self.num_envs)
             if self._img is None or self._img.shape[0] != hi - lo:
                 self._img = torch.empty((hi - lo, 200, 200, 3), dtype=torch.uint8, device=self.device)
@@ -428,7 +433,8 @@ class VecPlayEnv:
         """playEnv.step for every env.  With autoreset: the envs whose episode ended (time limit, fault, success, end_mask [N] != 0) are
         reset inside the call, on the device - obs holds their new episode's first observation, the reward / is_success the transition's;
         done is a bool [N] tensor, info['terminal_observation'] the ended envs' step observations (rows valid where done),
-        info['done_reason'] the int32 reasons (_lib.DONE_*), info['TimeLimit.truncated'] the envs that the time limit alone ended."""
+        info['done_reason'] the int32 reasons (_lib.DONE_*), info['TimeLimit.truncated'] the envs that the time limit alone ended.  After
+        set_image_obs the obs and, with autoreset, info['terminal_observation'] carry the camera images drawn inside the same call."""
         a = action.to(device=self.device, dtype=torch.float32).contiguous()
         assert a.shape == (self.num_envs, self.dims['action']), a.shape
         if self.autoreset:
@@ -458,6 +464,8 @@ class VecPlayEnv:
                 'TimeLimit.truncated': reason == _lib.DONE_TIME_LIMIT,      # gym 0.21: the time limit and nothing else ended the episode
                 'done_reason': reason,
                 'reset_row': self._reset_row}      # the table row each ended env restarted from, -1 elsewhere (and everywhere without a table)
+        if self.image_final is not None:
+            info['terminal_observation'].update(self._image_keys(self.image_final))
         return self._obs(), self.buf['reward'], reason != 0, info
 
     def set_reset_table(self, o):
@@ -874,6 +882,24 @@ class VecPlayEnv:
 
     unpack_segmentation = staticmethod(unpack_segmentation)
 
+    def _layer_args(self, who, n, width, height, layers, depth, camera, cameras, near, far):
+        """render_layers' and set_image_obs' host-side checks (ValueError): (the layers as a tuple, {layer: (shape, dtype)} for n envs, cameras contiguous or None)"""
+        layers = (layers,) if isinstance(layers, str) else tuple(layers)
+        shapes = {'rgb': ((n, height, width, 3), torch.uint8), 'depth': ((n, height, width), torch.float32), 'segmentation': ((n, height, width), torch.int32)}
+        if not layers or any(k not in shapes for k in layers):
+            raise ValueError('%s: layers are a non-empty choice of %s, not %r' % (who, sorted(shapes), layers))
+        if depth not in ('buffer', 'metres'):
+            raise ValueError("%s: depth is 'buffer' or 'metres', not %r" % (who, depth))
+        if camera is not None and cameras is not None:
+            raise ValueError('%s: camera or cameras, not both' % who)
+        if not (float(near) > 0.0 and float(far) > float(near)):
+            raise ValueError('%s: 0 < near < far, not near = %r, far = %r' % (who, near, far))
+        if cameras is not None:
+            if not (cameras.is_cuda and cameras.dtype == torch.float32 and tuple(cameras.shape) == (n, 11)):
+                raise ValueError('%s: cameras is a float32 device tensor [%d, 11], not %s %s on %s' % (who, n, cameras.dtype, tuple(cameras.shape), cameras.device))
+            cameras = cameras.contiguous()
+        return layers, shapes, cameras
+
     def render_layers(self, width=200, height=200, envs=None, camera=None, cameras=None, layers=('rgb', 'depth', 'segmentation'), depth='buffer', near=0.01,
                       far=10.0, sub_goal=None, ghost_arm=None, out=None):
         """the layers of getCameraImage for envs [lo, hi) (default: all) as a dict of device tensors: 'rgb' uint8 [n, height, width, 3] (render's image, byte for
@@ -883,20 +909,7 @@ class VecPlayEnv:
         tint rgb only.  out: a dict of preallocated tensors for some or all of the layers.  near / far shape the depth value only.  Nothing is read back."""
         lo, n, sub_goal, ghost_arm = self._render_args(envs, sub_goal, ghost_arm)
         width, height = int(width), int(height)
-        layers = (layers,) if isinstance(layers, str) else tuple(layers)
-        shapes = {'rgb': ((n, height, width, 3), torch.uint8), 'depth': ((n, height, width), torch.float32), 'segmentation': ((n, height, width), torch.int32)}
-        if not layers or any(k not in shapes for k in layers):
-            raise ValueError('render_layers: layers are a non-empty choice of %s, not %r' % (sorted(shapes), layers))
-        if depth not in ('buffer', 'metres'):
-            raise ValueError("render_layers: depth is 'buffer' or 'metres', not %r" % (depth,))
-        if camera is not None and cameras is not None:
-            raise ValueError('render_layers: camera or cameras, not both')
-        if not (float(near) > 0.0 and float(far) > float(near)):
-            raise ValueError('render_layers: 0 < near < far, not near = %r, far = %r' % (near, far))
-        if cameras is not None:
-            if not (cameras.is_cuda and cameras.dtype == torch.float32 and tuple(cameras.shape) == (n, 11)):
-                raise ValueError('render_layers: cameras is a float32 device tensor [%d, 11], not %s %s on %s' % (n, cameras.dtype, tuple(cameras.shape), cameras.device))
-            cameras = cameras.contiguous()
+        layers, shapes, cameras = self._layer_args('render_layers', n, width, height, layers, depth, camera, cameras, near, far)
         res = {}
         for k in layers:
             shape, dtype = shapes[k]
@@ -909,6 +922,47 @@ class VecPlayEnv:
                    _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, lo, n, _ptr(res.get('rgb')), _ptr(res.get('depth')),
                    _ptr(res.get('segmentation')), _ptr(sub_goal), _ptr(ghost_arm), self._stream())
         return res
+
+    @staticmethod
+    def _image_keys(t):
+        """the observation's image keys of a set_image_obs tensor dict: 'img' (the rgb tensor, None unless asked for), 'depth' and 'segmentation' where asked for"""
+        return {'img': t.get('rgb'), **{k: t[k] for k in ('depth', 'segmentation') if k in t}}
+
+    def set_image_obs(self, width=84, height=84, layers=('rgb',), camera=None, cameras=None, depth='buffer', near=0.01, far=10.0):
+        """Camera images as part of the observation (rp_set_image_obs): from now on step, reset, reset(o=...) and calc_state draw the chosen layers of every env whose
+        observation rows they write, inside the same library call and from the state those rows describe - byte for byte what render_layers(width, height, layers=...,
+        same camera arguments) gives right after the call, without ghosts, with set_visuals' table.  obs['img'] is then the rgb tensor uint8 [N, height, width, 3] (None
+        unless 'rgb' is among the layers), obs['depth'] float32 [N, height, width] and obs['segmentation'] int32 [N, height, width] exist where asked for.  A masked
+        reset redraws the masked envs' rows only.  With autoreset=True, obs holds an ended env's first frame of the new episode and info['terminal_observation'] gets
+        the same keys with the ended envs' LAST frame, drawn between the step and the reset (rows valid where done; the others keep what they held).  All these tensors
+        are owned like buf: the next call overwrites them (clone to keep).
+
+        camera: an rp_camera for all envs (self.camera(...), gripper=True included; None: the reference's fixed camera), or cameras: a float32 device tensor [N, 11]
+        (self.cameras(...)), kept as self.image_cameras and read on the device at every draw, so rows may be rewritten in place between calls (a new camera per
+        episode: image_cameras[done] = ...).  depth / near / far as render_layers'.  Host values are checked as render_layers checks them (ValueError).  While set,
+        record_images' 200 x 200 render is not made.  set_image_obs(None) switches the feature off: obs['img'] is None, or record_images' picture, again.  Switching on,
+        over or off may synchronise the device; the configuration is not part of get_state / set_state / clone_envs."""
+        if width is None:
+            self._call('rp_set_image_obs', None, None, 0.0, 0.0, 0, 0, 0, None, None, None, None, None, None)
+            self.image_obs = self.image_final = self.image_cameras = None
+            self._kept.pop('rp_set_image_obs', None)
+            return
+        N = self.num_envs
+        width, height = int(width), int(height)
+        if cameras is not None and isinstance(cameras, torch.Tensor) and not cameras.is_contiguous():
+            raise ValueError('set_image_obs: cameras must be contiguous (it is read in place at every draw)')
+        layers, shapes, cameras = self._layer_args('set_image_obs', N, width, height, layers, depth, camera, cameras, near, far)
+        if not (0 < width <= 4096 and 0 < height <= 4096):
+            raise ValueError('set_image_obs: width and height lie in 1 .. 4096, not %d x %d' % (width, height))
+
+        def alloc():
+            return {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
+        obs, final = alloc(), alloc() if self.autoreset else None
+        ptrs = [_ptr(t.get(k)) for t in (obs, final or {}) for k in ('rgb', 'depth', 'segmentation')]
+        self._call('rp_set_image_obs', C.byref(camera) if camera is not None else None, _ptr(cameras), float(near), float(far),
+                   _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, *ptrs)
+        self.image_obs, self.image_final, self.image_cameras = obs, final, cameras
+        self._kept['rp_set_image_obs'] = (obs, final, cameras)      # (kept until the next set: the library writes and reads them at every draw)
 
     def ray_test(self, ray_from, ray_to):
         """bullet_client.rayTest for k rays per env: ray_from / ray_to [N, k, 3] (world).  Returns dict(hit_fraction [N, k] (1 = miss),
