@@ -293,6 +293,34 @@ int rp_set_image_obs(rp_handle h, const rp_camera* cam, const float* cam_rows /*
                      float near_plane, float far_plane, int32_t depth_mode, int32_t width, int32_t height,
                      uint8_t* rgb, float* depth, int32_t* segmentation,                      /* [N, h, w, 3] / [N, h, w] / [N, h, w], each may be NULL, not all */
                      uint8_t* final_rgb, float* final_depth, int32_t* final_segmentation);   /* same shapes, each may be NULL: the ended envs' rows under rp_step_autoreset */
+/* ---- several camera views per env written by the same calls -----------------------------------------------------------------------------
+ * rp_set_image_obs for up to RP_MAX_IMAGE_VIEWS views at once (a fixed camera and the gripper camera, say, at different sizes and with different layers): its
+ * semantics view by view.  While set, rp_step and rp_calc_state draw every view of all envs, rp_reset and rp_reset_to every view of the mask's envs (on
+ * RP_ERR_INCOMPLETE too), on the call's stream, after the observations; rp_step_autoreset makes its TERMINAL PASS after k_autoreset_mark - the envs with done != 0, and
+ * only the views and layers whose final_* pointer is non-NULL - and its OBSERVATION PASS, all envs and every view, after the reset kernels.  Row e of every layer of view
+ * k is byte for byte what rp_render_layers(h, that view's cam, cam_rows, near_plane, far_plane, depth_mode, width, height, e, 1, ...) would write for env e at that
+ * moment, without ghosts and with the handle's visuals table; rows of unselected envs are not touched.
+ * The handle has ONE image configuration: rp_set_image_views and rp_set_image_obs each replace it, the latest call wins.  n_views == 0 (views may be NULL) switches the
+ * feature off, as rp_set_image_obs with width == 0 && height == 0 does.  The views array and each cam are copied at the call (cam NULL with no cam_rows =
+ * rp_default_camera; mode 1 = the gripper camera); cam_rows and the output buffers stay the caller's and stay referenced, as rp_set_image_obs' do.  Replacing or
+ * switching off a configuration in force synchronises the device first.  The configuration is not state: rp_get_state, rp_set_state and rp_copy_envs do not carry it;
+ * rp_destroy frees nothing new.  The pose table is reserved for N envs here: no stepping call allocates, waits for the host or reads device values.
+ * Cost: one view is rp_set_image_obs' configuration, with its two launches per pass.  Two or more views cost TWO launches per pass whatever their number: one
+ * k_collider_poses over the N envs - the poses do not depend on the camera - and one k_render_views whose grid holds the tiles of all views of the pass.
+ * RP_ERR_ARG (the configuration in force stays; the message names the view): n_views < 0 or > RP_MAX_IMAGE_VIEWS; views NULL with n_views > 0; for any view what
+ * rp_set_image_obs refuses (no layer, both cam and cam_rows, the size, camera, near / far and depth-mode errors); N times the SUM of the views' tile counts
+ * ceil(width / 16) * ceil(height / 16) > 2^31 - 1.  Shares the handle's one collider-pose table as rp_set_image_obs does: no overlap with a drawing call on another stream. */
+#define RP_MAX_IMAGE_VIEWS 4
+typedef struct rp_image_view {
+  const rp_camera* cam;        /* copied at the call; NULL with no cam_rows = rp_default_camera; mode 1 = gripper camera */
+  const float* cam_rows;       /* device [N, 11], caller-owned, read on the device at every draw; never both */
+  float near_plane, far_plane;
+  int32_t depth_mode;          /* rp_depth_mode */
+  int32_t width, height;       /* 1 .. 4096 each; views may differ */
+  uint8_t* rgb; float* depth; int32_t* segmentation;                    /* [N, h, w, 3] / [N, h, w] / [N, h, w]; each may be NULL, not all three */
+  uint8_t* final_rgb; float* final_depth; int32_t* final_segmentation;  /* same shapes, each may be NULL */
+} rp_image_view;
+int rp_set_image_views(rp_handle h, const rp_image_view* views, int32_t n_views);
 /* bullet_client.rayTest(from, to) (ENV:738-741) for k rays per env: from / to [N, k, 3] world coordinates.  Outputs (each may be NULL):
  * hit_fraction [N, k] (1 on a miss), collider [N, k] (index into the model's collider table, -1 on a miss), link [N, k] (Bullet link
  * index of an arm collider, -1 otherwise), hit_position [N, k, 3], hit_normal [N, k, 3].  A ray that starts inside a shape does not hit it. */

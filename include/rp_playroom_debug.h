@@ -32,6 +32,10 @@ int rp_debug_ghost_joints(rp_handle h, float* host_buf, int32_t num_envs);
 /* the render kernel's tile shortlist (rp_render, rp_render_ex and rp_render_layers alike: one kernel draws for all three): on = 1 (the default) a tile walks only the
  * records whose bounding sphere meets its frustum; on = 0 every record is on every tile's list.  The layers are bit-identical either way (tests/test_gpu_render_layers.py); tools/render_rate.py times one against the other. */
 int rp_debug_render_cull(rp_handle h, int32_t on);
+/* the image passes of rp_set_image_views with two or more views: on = 1 (the default) one k_render_views launch draws the tiles of all views of a pass; on = 0 one
+ * k_render_layers launch per view, behind the same single k_collider_poses.  The layers are bit-identical either way (tests/test_gpu_image_views.py);
+ * tools/image_views_rate.py times one against the other. */
+int rp_debug_image_views_merge(rp_handle h, int32_t on);
 /* rounds the most recent rp_reset took */
 int rp_debug_reset_rounds(rp_handle h);
 /* k_autoreset's launch shape, fixed at rp_create: *grid = its blocks (the blocks resident at once, or RP_AUTORESET_BLOCKS; never more than

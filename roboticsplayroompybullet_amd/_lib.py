@@ -74,6 +74,16 @@ class RpCamera(C.Structure):
                 ('mode', C.c_int32)]
 
 
+class RpImageView(C.Structure):
+    """rp_image_view (include/rp_playroom.h): one view of rp_set_image_views"""
+    _fields_ = [('cam', C.POINTER(RpCamera)), ('cam_rows', C.c_void_p), ('near_plane', C.c_float), ('far_plane', C.c_float), ('depth_mode', C.c_int32),
+                ('width', C.c_int32), ('height', C.c_int32), ('rgb', C.c_void_p), ('depth', C.c_void_p), ('segmentation', C.c_void_p),
+                ('final_rgb', C.c_void_p), ('final_depth', C.c_void_p), ('final_segmentation', C.c_void_p)]
+
+
+MAX_IMAGE_VIEWS = 4      # RP_MAX_IMAGE_VIEWS
+
+
 class RpTimers(C.Structure):
     _fields_ = [('last_step_ms', C.c_float), ('last_reset_ms', C.c_float), ('steps', C.c_uint64), ('steps_timed', C.c_uint32),
                 ('avg_step_ms', C.c_float), ('avg_action_ms', C.c_float), ('avg_prep_ms', C.c_float), ('avg_solve_ms', C.c_float),
@@ -86,10 +96,10 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset', 'rp_set_reset_table', 'rp_get_reset_rows',
            'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench',
            'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs',
-           'rp_get_visuals_dims', 'rp_set_visuals', 'rp_get_visuals', 'rp_set_image_obs']
+           'rp_get_visuals_dims', 'rp_set_visuals', 'rp_get_visuals', 'rp_set_image_obs', 'rp_set_image_views']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
-                 'rp_debug_autoreset_shape', 'rp_debug_action', 'rp_debug_render_cull']
+                 'rp_debug_autoreset_shape', 'rp_debug_action', 'rp_debug_render_cull', 'rp_debug_image_views_merge']
 
 _lib = None
 _libs = {}
@@ -159,6 +169,7 @@ def load(wide=False):
     lib.rp_render_ex.argtypes = [vp, C.POINTER(RpCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.rp_render_layers.argtypes = [vp, C.POINTER(RpCamera), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_set_image_obs.argtypes = [vp, C.POINTER(RpCamera), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+    lib.rp_set_image_views.argtypes = [vp, C.POINTER(RpImageView), C.c_int32]
     lib.rp_ray_test.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_debug_substep.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
     lib.rp_set_fused.argtypes = [vp, C.c_int32]
@@ -170,6 +181,7 @@ def load(wide=False):
     lib.rp_debug_autoreset_shape.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.rp_debug_action.argtypes = [vp, vp, vp]
     lib.rp_debug_render_cull.argtypes = [vp, C.c_int32]
+    lib.rp_debug_image_views_merge.argtypes = [vp, C.c_int32]
     _libs[path] = lib
     if not wide:
         _lib = lib

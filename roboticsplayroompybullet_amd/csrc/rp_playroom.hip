@@ -81,6 +81,11 @@ struct rp_sim {
   float* rt_tab; int rt_rows, rt_n_o; int* rt_cursor; int* rt_env_row; unsigned long long* rt_wave_bal; int* rt_wave_row; int rt_grid;
   rp_timers timers;
   char err[256];
+  /* (behind everything else: the kilobyte of tables moves no older field)
+   * rp_set_image_views with two or more views (io_on = 2; the handle has ONE image configuration, this one or rp_set_image_obs'): k_render_views' table of the observation
+   * pass and that of the terminal pass - the views with a final_* pointer, with those pointers, iv_fn of them -, each with its tile count; built at the set call */
+  RpViewTable iv_obs, iv_fin; int iv_n, iv_fn, iv_tiles, iv_ftiles;
+  int iv_nomerge;          /* rp_debug_image_views_merge(h, 0): a k_render_layers launch per view instead of one k_render_views */
 };
 
 #define EV_PER_STEP (2 + 2 * (2 * K_NSUB + 2))   /* step pair + a pair per launch (action, 12 prep, 12 solve, obs) */
@@ -136,6 +141,7 @@ static int table_get(rp_sim* h, const float* tab, TabCols<float> c, void* stream
 }
 
 static void image_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s);      /* (beside the render entry points, below) */
+static void views_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s);
 
 static OutPtrs to_ptrs(const rp_out* o) {
   OutPtrs p;
@@ -1083,10 +1089,31 @@ static void views_launch(rp_handle h, const RpViews& v, int first_env, uint8_t* 
                      (const int*)sel32, sel8);
 }
 
+/* rp_set_image_views' draw (two or more views): ONE k_collider_poses over all N envs - the poses and rc_ee do not depend on the camera - and ONE k_render_views whose
+ * grid holds the tiles of every view of the pass; with rp_debug_image_views_merge(h, 0) a k_render_layers launch per view behind the same pose launch.  Same bytes. */
+static void views_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
+  const RpViewTable& t = final ? h->iv_fin : h->iv_obs;
+  const int n = final ? h->iv_fn : h->iv_n, tiles = final ? h->iv_ftiles : h->iv_tiles, N = h->cfg.num_envs, cull = h->render_nocull ? 0 : 1;
+  const bool sel = sel32 || sel8;
+  hipLaunchKernelGGL(sel ? k_collider_poses<true> : k_collider_poses<false>, dim3(N), dim3(64), 0, s, h->dev_model, h->state, 0, N, h->rc_tab, h->rc_cnt, (const float*)nullptr,
+                     h->rc_ee, (const float*)nullptr, (const float*)h->vis, (const int*)sel32, sel8);
+  if (!h->iv_nomerge) {
+    hipLaunchKernelGGL(sel ? k_render_views<true> : k_render_views<false>, dim3((unsigned)N * (unsigned)tiles), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, N, t, n, tiles,
+                       h->rc_ee, cull, (const float*)h->vis, (const int*)sel32, sel8);
+    return;
+  }
+  for (int k = 0; k < n; k++) {
+    const RpViewEntry& e = t.v[k];
+    hipLaunchKernelGGL(sel ? k_render_layers<true> : k_render_layers<false>, dim3((unsigned)N * (unsigned)e.tiles), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, N, e.cam,
+                       e.cam_rows, h->rc_ee, e.width, e.height, cull, e.near_plane, e.far_plane, e.metres, e.rgb, e.depth, e.seg, (const float*)h->vis, 0, (const int*)sel32, sel8);
+  }
+}
+
 /* rp_set_image_obs' draw inside a call that writes observation rows: all N envs, or those sel32 / sel8 select on the device, into the observation arrays (final = false)
  * or the ended envs' (final = true: rp_step_autoreset's terminal pass).  Two launches on `s`; nothing is checked, reserved or read back here. */
 static void image_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
   if (!h->io_on || (final && !h->io_final)) return;
+  if (h->io_on == 2) { views_pass(h, final, sel32, sel8, s); return; }
   if (final) views_launch(h, h->io, 0, h->io_frgb, h->io_fdepth, h->io_fseg, nullptr, nullptr, sel32, sel8, s);
   else views_launch(h, h->io, 0, h->io_rgb, h->io_depth, h->io_seg, nullptr, nullptr, sel32, sel8, s);
 }
@@ -1146,6 +1173,59 @@ int rp_set_image_obs(rp_handle h, const rp_camera* cam, const float* cam_rows, f
   h->io_on = 1;
   return RP_OK;
 }
+
+/* Several views per env.  One view is rp_set_image_obs' configuration and takes its path and its launches; two or more fill k_render_views' two tables here, so that
+ * a stepping call only launches (views_pass).  Every view is checked before anything changes: a refusal leaves the configuration in force as it was. */
+int rp_set_image_views(rp_handle h, const rp_image_view* views, int32_t n_views) {
+  if (!h) return RP_ERR_ARG;
+  if (n_views < 0 || n_views > RP_MAX_IMAGE_VIEWS) { snprintf(h->err, 256, "rp_set_image_views: n_views = %d lies outside 0 .. %d", n_views, RP_MAX_IMAGE_VIEWS); return RP_ERR_ARG; }
+  if (n_views == 0) return rp_set_image_obs(h, nullptr, nullptr, 0.f, 0.f, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (!views) { snprintf(h->err, 256, "rp_set_image_views: views is NULL with n_views = %d", n_views); return RP_ERR_ARG; }
+  const int N = h->cfg.num_envs;
+  RpViewTable obs, fin;
+  memset(&obs, 0, sizeof(obs)); memset(&fin, 0, sizeof(fin));
+  int nf = 0; long long tiles = 0, ftiles = 0;
+  for (int k = 0; k < n_views; k++) {
+    const rp_image_view& w = views[k];
+    char who[48];
+    snprintf(who, sizeof(who), "rp_set_image_views: view %d", k);
+    const char* bad = layers_complaint(w.cam, w.cam_rows, w.near_plane, w.far_plane, w.depth_mode, w.rgb, w.depth, w.segmentation);
+    if (bad) { snprintf(h->err, 256, "%s: %s", who, bad); return RP_ERR_ARG; }
+    RpViews v;
+    int rc = views_check(h, who, w.cam, w.cam_rows, w.near_plane, w.far_plane, w.depth_mode == RP_DEPTH_METRES ? 1 : 0, w.width, w.height, 0, N, nullptr, &v);
+    if (rc != RP_OK) return rc;
+    RpViewEntry e;
+    memset(&e, 0, sizeof(e));
+    e.cam = v.cam; e.cam_rows = v.cam_rows; e.width = v.width; e.height = v.height;
+    e.tiles_x = (v.width + 15) / 16; e.tiles = e.tiles_x * ((v.height + 15) / 16);
+    e.near_plane = v.near_plane; e.far_plane = v.far_plane; e.metres = v.metres;
+    e.tile0 = (int)tiles; e.rgb = w.rgb; e.depth = w.depth; e.seg = w.segmentation;
+    obs.v[k] = e;
+    tiles += e.tiles;
+    if (w.final_rgb || w.final_depth || w.final_segmentation) {
+      e.tile0 = (int)ftiles; e.rgb = w.final_rgb; e.depth = w.final_depth; e.seg = w.final_segmentation;
+      fin.v[nf++] = e;
+      ftiles += e.tiles;
+    }
+  }
+  if ((long long)N * tiles > 0x7fffffffLL) { snprintf(h->err, 256, "rp_set_image_views: %lld tiles of %d views exceed one launch", (long long)N * tiles, n_views); return RP_ERR_ARG; }
+  if (n_views == 1) {
+    const rp_image_view& w = views[0];
+    return rp_set_image_obs(h, w.cam, w.cam_rows, w.near_plane, w.far_plane, w.depth_mode, w.width, w.height, w.rgb, w.depth, w.segmentation, w.final_rgb, w.final_depth,
+                            w.final_segmentation);
+  }
+  DevGuard guard(h->cfg.device);
+  if (h->io_on) HIPCHK(h, hipDeviceSynchronize());
+  int rc = rc_reserve(h, N);
+  if (rc != RP_OK) { h->io_on = 0; h->io_final = 0; return rc; }      /* (the table it had may be gone) */
+  h->iv_obs = obs; h->iv_fin = fin; h->iv_n = n_views; h->iv_fn = nf; h->iv_tiles = (int)tiles; h->iv_ftiles = (int)ftiles;
+  h->io_final = nf > 0 ? 1 : 0;
+  h->io_on = 2;
+  return RP_OK;
+}
+
+/* test seam and benchmark control: on = 0 draws the views of a pass as one k_render_layers launch each (the default is on: one k_render_views launch) */
+int rp_debug_image_views_merge(rp_handle h, int32_t on) { if (!h) return RP_ERR_ARG; h->iv_nomerge = on ? 0 : 1; return RP_OK; }
 
 int rp_render_ex(rp_handle h, const rp_camera* cam, int32_t width, int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb,
                  const float* sub_goal, const float* ghost_arm, void* stream) {

@@ -12,7 +12,8 @@
  *                      where rp_set_visuals made a table
  *   k_render_layers    a 16 x 16 pixel tile per block, the tile's shortlist of records in LDS, nearest hit per pixel: colour, depth and segmentation; per-env
  *                      cameras (rp_render, rp_render_ex: the colour alone; rp_render_layers)
- *                      both as <SEL = true> too: the envs a device array selects (rp_set_image_obs: the ended envs' terminal frames, a masked reset's images)
+ *   k_render_views     the tiles of up to four views of the same envs in one launch, behind one k_collider_poses (rp_set_image_views)
+ *                      all three as <SEL = true> too: the envs a device array selects (rp_set_image_obs: the ended envs' terminal frames, a masked reset's images)
  *   k_ray_test         K rays per env against the same table: hit fraction, position, normal, collider, Bullet link index */
 #pragma once
 
@@ -251,22 +252,16 @@ __device__ __forceinline__ void rc_gripper_basis(const M3& R, V3& fwd, V3& right
  * sel32, sel8 (each may be null): k_collider_poses' selection, by env `first + slot`; every tile's block of an unselected env leaves before the view is built - all 256
  * threads, ahead of the first barrier - and the env's rows of rgb / depth / seg keep what they held. */
 static_assert(RC_MAX <= 256, "k_render_layers: one lane per record");
-template <bool SEL>
-__global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, int num, RpCamera cam,
-                                                       const float* __restrict__ cam_rows, const float* __restrict__ ee_pose, int width, int height, int cull,
-                                                       float near_plane, float far_plane, int metres, unsigned char* __restrict__ rgb, float* __restrict__ depth,
-                                                       int* __restrict__ seg, const float* __restrict__ vis, int first, const int* __restrict__ sel32,
-                                                       const unsigned char* __restrict__ sel8) {
+/* one tile of one env, everything behind the kernels' split of blockIdx.x: the view, the shortlist, the pixels (the comment above).  k_render_layers and k_render_views
+ * both draw through it, so a row is the same bytes whichever kernel wrote it; inlined, each kernel owns its copy of the LDS arrays. */
+__device__ __forceinline__ void rc_draw_tile(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, const RpCamera& cam,
+                                             const float* __restrict__ cam_rows, const float* __restrict__ ee_pose, int width, int height, int cull, float near_plane,
+                                             float far_plane, int metres, unsigned char* __restrict__ rgb, float* __restrict__ depth, int* __restrict__ seg,
+                                             const float* __restrict__ vis, int first, int slot, int tile, int tiles_x) {
   __shared__ float T[RC_MAX * RC_STRIDE];      /* the shortlist's records, compacted */
   __shared__ float V[14 + VIS_TAIL];           /* eye, fwd, right, up, tan_half_fov, aspect; light direction, ambient, diffuse, background */
   __shared__ int list[RC_MAX];
   __shared__ int wcnt[4];
-  const int tiles_x = (width + 15) >> 4, tiles = tiles_x * ((height + 15) >> 4);
-  /* tile-major: consecutive blocks are the SAME tile of consecutive envs.  Blocks go to the eight XCDs round robin; env-major, with a tile count that is a multiple of
-   * eight (64 x 64: 16), the few tiles that hold the arm - whose hulls cost a ray hundreds of plane tests - would always land on the same XCDs */
-  const int tile = blockIdx.x / num, slot = blockIdx.x - tile * num;
-  if (tile >= tiles) return;
-  if (SEL && !rc_selected(sel32, sel8, first + slot)) return;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) {
@@ -379,6 +374,54 @@ __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restric
     const int id = bi >= 0 ? __float_as_int(T[bi * RC_STRIDE + 19]) : 0;
     seg[pix] = bi >= 0 ? ((id & 0xFF) | (((id >> 8) + 1) << 24)) : -1;
   }
+}
+
+
+template <bool SEL>
+__global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, int num, RpCamera cam,
+                                                       const float* __restrict__ cam_rows, const float* __restrict__ ee_pose, int width, int height, int cull,
+                                                       float near_plane, float far_plane, int metres, unsigned char* __restrict__ rgb, float* __restrict__ depth,
+                                                       int* __restrict__ seg, const float* __restrict__ vis, int first, const int* __restrict__ sel32,
+                                                       const unsigned char* __restrict__ sel8) {
+  const int tiles_x = (width + 15) >> 4, tiles = tiles_x * ((height + 15) >> 4);
+  /* tile-major: consecutive blocks are the SAME tile of consecutive envs.  Blocks go to the eight XCDs round robin; env-major, with a tile count that is a multiple of
+   * eight (64 x 64: 16), the few tiles that hold the arm - whose hulls cost a ray hundreds of plane tests - would always land on the same XCDs */
+  const int tile = blockIdx.x / num, slot = blockIdx.x - tile * num;
+  if (tile >= tiles) return;
+  if (SEL && !rc_selected(sel32, sel8, first + slot)) return;
+  rc_draw_tile(m, tab, cnt, cam, cam_rows, ee_pose, width, height, cull, near_plane, far_plane, metres, rgb, depth, seg, vis, first, slot, tile, tiles_x);
+}
+
+/* rp_set_image_views: up to RC_MAX_VIEWS views of the same envs in ONE launch, behind one k_collider_poses (the poses and ee_pose do not depend on the camera).  The
+ * table travels by value in the kernel arguments; the host builds it once, at the set call.  tile0: the view's first tile in the list of all views' tiles, one behind
+ * the other; every view covers the same `num` envs, slot = env (first = 0). */
+#define RC_MAX_VIEWS 4
+struct RpViewEntry {
+  RpCamera cam; const float* cam_rows;
+  int width, height, tiles_x, tiles, tile0;
+  float near_plane, far_plane; int metres;
+  unsigned char* rgb; float* depth; int* seg;
+};
+struct RpViewTable { RpViewEntry v[RC_MAX_VIEWS]; };
+
+/* Block numbering as k_render_layers', tile-major over the CONCATENATED tile list: consecutive blocks are the same tile of the same view for consecutive envs, and the
+ * long tiles of one view (the arm's) run beside the short ones of another instead of ending a launch of their own.  The view of a block is found by at most three
+ * block-uniform compares; an unselected env's block leaves right after the split, before the table is read.  The rest is rc_draw_tile: the bytes of
+ * k_render_layers(that view's arguments). */
+template <bool SEL>
+__global__ void __launch_bounds__(256) k_render_views(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, int num,
+                                                      const RpViewTable vt, int n_views, int total_tiles, const float* __restrict__ ee_pose, int cull,
+                                                      const float* __restrict__ vis, const int* __restrict__ sel32, const unsigned char* __restrict__ sel8) {
+  const int g = blockIdx.x / num, slot = blockIdx.x - g * num;
+  if (g >= total_tiles) return;
+  if (SEL && !rc_selected(sel32, sel8, slot)) return;
+  int k = 0;
+  if (n_views > 1 && g >= vt.v[1].tile0) k = 1;
+  if (n_views > 2 && g >= vt.v[2].tile0) k = 2;
+  if (n_views > 3 && g >= vt.v[3].tile0) k = 3;
+  const RpViewEntry& e = vt.v[k];
+  rc_draw_tile(m, tab, cnt, e.cam, e.cam_rows, ee_pose, e.width, e.height, cull, e.near_plane, e.far_plane, e.metres, e.rgb, e.depth, e.seg, vis, 0, slot, g - e.tile0,
+               e.tiles_x);
 }
 
 /* rayTest (environments.py:738-741) for K rays per env: from / to [num][K][3]; fraction 1 and collider -1 on a miss */

@@ -349,6 +349,9 @@ class VecPlayEnv:
         self.image_obs = None               # set_image_obs: {'rgb' / 'depth' / 'segmentation': the tensors step / reset / calc_state write}, owned like buf
         self.image_final = None             # ... and under autoreset the ended envs' last frames (info['terminal_observation'])
         self.image_cameras = None           # ... and its per-env cameras [N, 11], read on the device at every draw: rewrite rows in place
+        self.image_views = None             # set_image_views: {name: {layer: tensor}}, obs['views']; the handle has this configuration or set_image_obs', never both
+        self.image_views_final = None       # ... under autoreset {name: {layer: tensor}} of the views with terminal frames (info['terminal_observation']['views'])
+        self.image_view_cameras = {}        # ... {name: the per-env cameras [N, 11]} of the views that have them: rewrite rows in place
         self.autoreset = bool(autoreset)
         if self.autoreset:
             limit = self._max_episode_steps if max_episode_steps is None else int(max_episode_steps)
@@ -379,7 +382,10 @@ class VecPlayEnv:
         o = {k: self.buf[k] for k in OBS_KEYS}
         # environments.py:841-845: img only while record_images is set (render('rgb_array')); all envs, [N, 200, 200, 3] uint8
         o['img'] = None
-        if self.image_obs is not None:      # set_image_obs: the library drew them inside the call that wrote buf
+        if self.image_views is not None:    # set_image_views: the library drew every view inside the call that wrote buf
+            o['views'] = self.image_views
+            o['img'] = self.image_views.get('img', {}).get('rgb')
+        elif self.image_obs is not None:    # set_image_obs: the library drew them inside the call that wrote buf
             o.update(self._image_keys(self.image_obs))
         elif self.record_images:
             lo, hi = self.image_envs or (0, self.num_envs)
@@ -466,6 +472,8 @@ class VecPlayEnv:
                 'reset_row': self._reset_row}      # the table row each ended env restarted from, -1 elsewhere (and everywhere without a table)
         if self.image_final is not None:
             info['terminal_observation'].update(self._image_keys(self.image_final))
+        if self.image_views_final is not None:
+            info['terminal_observation']['views'] = self.image_views_final
         return self._obs(), self.buf['reward'], reason != 0, info
 
     def set_reset_table(self, o):
@@ -944,8 +952,7 @@ class VecPlayEnv:
         over or off may synchronise the device; the configuration is not part of get_state / set_state / clone_envs."""
         if width is None:
             self._call('rp_set_image_obs', None, None, 0.0, 0.0, 0, 0, 0, None, None, None, None, None, None)
-            self.image_obs = self.image_final = self.image_cameras = None
-            self._kept.pop('rp_set_image_obs', None)
+            self._no_images()
             return
         N = self.num_envs
         width, height = int(width), int(height)
@@ -961,8 +968,69 @@ class VecPlayEnv:
         ptrs = [_ptr(t.get(k)) for t in (obs, final or {}) for k in ('rgb', 'depth', 'segmentation')]
         self._call('rp_set_image_obs', C.byref(camera) if camera is not None else None, _ptr(cameras), float(near), float(far),
                    _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, *ptrs)
+        self._no_images()      # (the handle has one image configuration: this call replaced set_image_views' too)
         self.image_obs, self.image_final, self.image_cameras = obs, final, cameras
         self._kept['rp_set_image_obs'] = (obs, final, cameras)      # (kept until the next set: the library writes and reads them at every draw)
+
+    def _no_images(self):
+        """forget the tensors of the image configuration the library has just dropped (set_image_obs' or set_image_views': the handle holds one)"""
+        self.image_obs = self.image_final = self.image_cameras = None
+        self.image_views = self.image_views_final = None
+        self.image_view_cameras = {}
+        self._kept.pop('rp_set_image_obs', None)
+
+    def set_image_views(self, views):
+        """Several camera views per env as part of the observation (rp_set_image_views): views is an ordered mapping of 1 to 4 names to dicts of set_image_obs' keyword
+        arguments (width, height, layers, camera, cameras, depth, near, far; set_image_obs' defaults), e.g. {'img': dict(width=84, height=84), 'wrist': dict(width=64,
+        height=64, layers=('rgb', 'depth'), camera=env.camera(gripper=True))}.  From now on step, reset, reset(o=...) and calc_state draw every view of the envs whose
+        observation rows they write, inside the same library call - with two or more views one pose launch and one draw launch for all of them -, each view byte for
+        byte what render_layers gives with that view's arguments.  obs['views'][name] is {layer: tensor}; obs['img'] is the rgb tensor of the view named 'img' if there
+        is one, else None; obs['depth'] / obs['segmentation'] are absent.  With autoreset=True info['terminal_observation']['views'] has the same shape with the ended
+        envs' last frames (rows valid where done); a view given terminal=False has no terminal tensors and is left out of the terminal pass.  Host values are checked
+        per view as set_image_obs checks them; a ValueError names the view.  self.image_view_cameras[name] is the per-env camera tensor of a view that has one: rows
+        may be rewritten in place between calls.  While set, record_images' 200 x 200 render is not made.  The handle has ONE image configuration: set_image_views
+        replaces set_image_obs' and the reverse; set_image_views(None) and set_image_obs(None) both switch it off."""
+        if views is None:
+            self._call('rp_set_image_views', None, 0)
+            self._no_images()
+            return
+        if not hasattr(views, 'items') or not 1 <= len(views) <= _lib.MAX_IMAGE_VIEWS:
+            raise ValueError('set_image_views: views is a mapping of 1 to %d names to dicts of set_image_obs\' arguments' % _lib.MAX_IMAGE_VIEWS)
+        N = self.num_envs
+        arr = (_lib.RpImageView * len(views))()
+        obs, final, cams, keep = {}, {}, {}, []
+        defaults = dict(width=84, height=84, layers=('rgb',), camera=None, cameras=None, depth='buffer', near=0.01, far=10.0, terminal=True)
+        for i, (name, kw) in enumerate(views.items()):
+            who = 'set_image_views: view %r' % (name,)
+            if not hasattr(kw, 'keys') or set(kw) - set(defaults):
+                raise ValueError('%s: a dict with keys among %s, not %r' % (who, sorted(defaults), kw))
+            a = {**defaults, **kw}
+            width, height, cameras = int(a['width']), int(a['height']), a['cameras']
+            if cameras is not None and isinstance(cameras, torch.Tensor) and not cameras.is_contiguous():
+                raise ValueError('%s: cameras must be contiguous (it is read in place at every draw)' % who)
+            layers, shapes, cameras = self._layer_args(who, N, width, height, a['layers'], a['depth'], a['camera'], cameras, a['near'], a['far'])
+            if not (0 < width <= 4096 and 0 < height <= 4096):
+                raise ValueError('%s: width and height lie in 1 .. 4096, not %d x %d' % (who, width, height))
+            obs[name] = {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
+            if self.autoreset and a['terminal']:
+                final[name] = {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
+            if cameras is not None:
+                cams[name] = cameras
+            v = arr[i]
+            if a['camera'] is not None:
+                keep.append(a['camera'])
+                v.cam = C.pointer(a['camera'])
+            v.cam_rows = cameras.data_ptr() if cameras is not None else None
+            v.near_plane, v.far_plane, v.depth_mode = float(a['near']), float(a['far']), _lib.DEPTH_METRES if a['depth'] == 'metres' else _lib.DEPTH_BUFFER
+            v.width, v.height = width, height
+            for k in layers:
+                setattr(v, k, obs[name][k].data_ptr())
+                if name in final:
+                    setattr(v, 'final_' + k, final[name][k].data_ptr())
+        self._call('rp_set_image_views', arr, len(views))
+        self._no_images()
+        self.image_views, self.image_views_final, self.image_view_cameras = obs, (final if self.autoreset else None), cams
+        self._kept['rp_set_image_obs'] = (obs, final, cams)      # (the one image configuration's tensors, kept until the next set or switch-off)
 
     def ray_test(self, ray_from, ray_to):
         """bullet_client.rayTest for k rays per env: ray_from / ray_to [N, k, 3] (world).  Returns dict(hit_fraction [N, k] (1 = miss),
