@@ -321,6 +321,57 @@ typedef struct rp_image_view {
   uint8_t* final_rgb; float* final_depth; int32_t* final_segmentation;  /* same shapes, each may be NULL */
 } rp_image_view;
 int rp_set_image_views(rp_handle h, const rp_image_view* views, int32_t n_views);
+/* ---- per-env point clouds from the camera views ---------------------------------------------------------------------------------------------
+ * A fixed number P = max_points of points per env, compacted on the device from a view's depth (RP_DEPTH_METRES: eye-space z) and segmentation layers by kernel
+ * k_point_cloud, one block per (env, view), behind the draw that wrote the layers.  THE RULE, for one env and one view of width x height:
+ *   pixels are taken in row-major order, i = y * width + x.  Pixel i is VALID iff segmentation[i] != -1 (a hit), bit (segmentation[i] & 0xFF) of drop is clear (its
+ *   collider is not dropped) and (max_depth <= 0 || depth[i] <= max_depth).  n = the number of valid pixels, r(i) = the rank of a valid pixel among the valid ones.
+ *   n <= P: slot r(i) takes pixel i; slots n .. P - 1 are PADDING: xyz = (0, 0, 0), point_seg = -1, point_rgb = (0, 0, 0).
+ *   n >  P: slot j (0 <= j < P) takes the valid pixel of rank floor(j * n / P), in 64-bit integers: an even, deterministic stride through the hits in scan order
+ *           (slot 0 is always the first hit).
+ *   count = n, NOT capped at P: min(count, P) slots hold points, and count / P is the subsampling ratio.
+ * Which pixel lands in which slot is integer logic: exact, no atomics, the same on every run.  Per point: point_seg = the pixel's packed segmentation value
+ * (collider | (link + 1) << 24), point_rgb = the pixel's three bytes of the rgb layer, and xyz in float32, operation by operation without contraction, with the
+ * renderer's own expressions nx = (2 (x + 0.5) / width - 1) tan_half_fov aspect, ny = (1 - 2 (y + 0.5) / height) tan_half_fov, z = depth[i]:
+ *   RP_POINTS_CAMERA  (nx z, ny z, z) along the camera's (right, up, forward): the third component is the depth value bit for bit
+ *   RP_POINTS_WORLD   eye + ((forward + right nx) + up ny) z, component by component, with the basis the renderer built for that env: the launch's camera, the env's
+ *                     row of cam_rows (in double), or for the gripper camera (mode 1) the basis at the env's EE link - which the library does not expose otherwise.
+ * rp_render_points draws and compacts in one call: k_collider_poses, k_render_layers (RP_DEPTH_METRES, near 0.01, far 10, no ghosts, the handle's visuals table) into
+ * the CALLER'S layer buffers depth and segmentation [num_envs, height, width] - both required; rgb [num_envs, height, width, 3] may be NULL unless point_rgb is wanted -
+ * and k_point_cloud into xyz [num_envs, P, 3] float, point_seg [num_envs, P] int32, point_rgb [num_envs, P, 3] uint8, count [num_envs] int32 (each may be NULL, not both
+ * xyz and count).  cam / cam_rows, width, height, first_env, num_envs as for rp_render_layers.  Three launches on `stream`; no host wait, no host read of device values.
+ * RP_ERR_ARG: spec NULL, max_points outside 1 .. 65536, an unknown frame, max_depth not a number; depth or segmentation NULL; xyz and count both NULL; point_rgb without
+ * rgb; rp_render_layers' size, range and camera errors (both cam and cam_rows among them).  Shares the handle's one collider-pose table: do not overlap it with a
+ * call that draws on another stream. */
+enum rp_points_frame { RP_POINTS_WORLD = 0, RP_POINTS_CAMERA = 1 };
+typedef struct rp_points_spec {
+  int32_t max_points;   /* P, 1 .. 65536 */
+  int32_t frame;        /* rp_points_frame */
+  float max_depth;      /* metres of eye-space z; <= 0: no limit */
+  uint64_t drop;        /* bit c: drop pixels whose hit collider is c (RP_MAX_COL = 64) */
+} rp_points_spec;
+int rp_render_points(rp_handle h, const rp_camera* cam, const float* cam_rows /* device [num_envs, 11] or NULL */,
+                     int32_t width, int32_t height, int32_t first_env, int32_t num_envs, const rp_points_spec* spec,
+                     uint8_t* rgb /* layer buffer [num_envs, height, width, 3] or NULL */,
+                     float* depth /* layer buffer [num_envs, height, width], required */,
+                     int32_t* segmentation /* layer buffer [num_envs, height, width], required */,
+                     float* xyz /* [num_envs, P, 3] */, int32_t* point_seg /* [num_envs, P] */, uint8_t* point_rgb /* [num_envs, P, 3] */,
+                     int32_t* count /* [num_envs] */, void* stream);
+/* Attaches a cloud to view `view` of the image configuration IN FORCE (rp_set_image_obs' configuration is view 0; rp_set_image_views' views count from 0); spec NULL
+ * detaches it.  While attached, every image pass - rp_step, rp_calc_state, the masked rp_reset / rp_reset_to, both passes of rp_step_autoreset - launches ONE more
+ * k_point_cloud behind its draw: one launch for all attached views of the pass, with the pass's selection, from the layers the pass has just written.  The
+ * observation pass writes xyz / point_seg / point_rgb / count [N, ...] (shapes as rp_render_points', each may be NULL, not both xyz and count); the terminal pass
+ * writes final_* for the envs with done != 0 only, where any final_* is given (all four NULL: no terminal cloud).  Rows of unselected envs keep what they held.  A row
+ * is what rp_render_points with the view's camera arguments would write for that env at that moment.  The buffers are caller-owned and stay referenced.
+ * Cost: one launch per pass, no host wait, no host read of device values, no allocation.  Any later rp_set_image_obs or rp_set_image_views, switching off included,
+ * drops ALL attachments, after the synchronisation those calls make; replacing or detaching an attachment synchronises the device first.  Not state: rp_get_state,
+ * rp_set_state and rp_copy_envs do not carry it.  A handle that never calls this launches exactly what it launched before.
+ * RP_ERR_ARG (the attachments stay as they were; the message names the cause): no configuration in force; view out of range; a bad spec (as rp_render_points); the
+ * view's depth layer missing or not in RP_DEPTH_METRES; its segmentation layer missing; xyz and count both NULL; point_rgb given but the view has no rgb layer; a
+ * final_* output given but the view lacks the final depth or segmentation layer, or final_point_rgb without the final rgb layer. */
+int rp_set_image_points(rp_handle h, int32_t view, const rp_points_spec* spec,
+                        float* xyz, int32_t* point_seg, uint8_t* point_rgb, int32_t* count,
+                        float* final_xyz, int32_t* final_point_seg, uint8_t* final_point_rgb, int32_t* final_count);
 /* bullet_client.rayTest(from, to) (ENV:738-741) for k rays per env: from / to [N, k, 3] world coordinates.  Outputs (each may be NULL):
  * hit_fraction [N, k] (1 on a miss), collider [N, k] (index into the model's collider table, -1 on a miss), link [N, k] (Bullet link
  * index of an arm collider, -1 otherwise), hit_position [N, k, 3], hit_normal [N, k, 3].  A ray that starts inside a shape does not hit it. */

@@ -84,6 +84,16 @@ class RpImageView(C.Structure):
 MAX_IMAGE_VIEWS = 4      # RP_MAX_IMAGE_VIEWS
 
 
+class RpPointsSpec(C.Structure):
+    """rp_points_spec (include/rp_playroom.h): what rp_render_points / rp_set_image_points keep of a view's hits"""
+    _fields_ = [('max_points', C.c_int32), ('frame', C.c_int32), ('max_depth', C.c_float), ('drop', C.c_uint64)]
+
+
+# rp_points_frame (include/rp_playroom.h)
+POINTS_WORLD, POINTS_CAMERA = 0, 1
+MAX_POINTS = 65536       # rp_points_spec.max_points' upper limit
+
+
 class RpTimers(C.Structure):
     _fields_ = [('last_step_ms', C.c_float), ('last_reset_ms', C.c_float), ('steps', C.c_uint64), ('steps_timed', C.c_uint32),
                 ('avg_step_ms', C.c_float), ('avg_action_ms', C.c_float), ('avg_prep_ms', C.c_float), ('avg_solve_ms', C.c_float),
@@ -96,7 +106,8 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_set_autoreset', 'rp_get_episode_steps', 'rp_set_episode_steps', 'rp_step_autoreset', 'rp_set_reset_table', 'rp_get_reset_rows',
            'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench',
            'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs',
-           'rp_get_visuals_dims', 'rp_set_visuals', 'rp_get_visuals', 'rp_set_image_obs', 'rp_set_image_views']
+           'rp_get_visuals_dims', 'rp_set_visuals', 'rp_get_visuals', 'rp_set_image_obs', 'rp_set_image_views',
+           'rp_render_points', 'rp_set_image_points']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
                  'rp_debug_autoreset_shape', 'rp_debug_action', 'rp_debug_render_cull', 'rp_debug_image_views_merge']
@@ -170,6 +181,8 @@ def load(wide=False):
     lib.rp_render_layers.argtypes = [vp, C.POINTER(RpCamera), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_set_image_obs.argtypes = [vp, C.POINTER(RpCamera), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_set_image_views.argtypes = [vp, C.POINTER(RpImageView), C.c_int32]
+    lib.rp_render_points.argtypes = [vp, C.POINTER(RpCamera), vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RpPointsSpec), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rp_set_image_points.argtypes = [vp, C.c_int32, C.POINTER(RpPointsSpec), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rp_ray_test.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_debug_substep.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
     lib.rp_set_fused.argtypes = [vp, C.c_int32]

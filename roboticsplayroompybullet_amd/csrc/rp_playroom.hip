@@ -86,6 +86,10 @@ struct rp_sim {
    * pass and that of the terminal pass - the views with a final_* pointer, with those pointers, iv_fn of them -, each with its tile count; built at the set call */
   RpViewTable iv_obs, iv_fin; int iv_n, iv_fn, iv_tiles, iv_ftiles;
   int iv_nomerge;          /* rp_debug_image_views_merge(h, 0): a k_render_layers launch per view instead of one k_render_views */
+  int iv_fmap[RC_MAX_VIEWS];      /* view -> its entry of iv_fin, -1: the view has no terminal layers */
+  /* rp_set_image_points: the clouds attached to the views of the image configuration in force (pc_n = how many views have one; 0: image_pass launches what it always
+   * launched).  pc_obs[k] / pc_fin[k] are view k's entries for the observation and the terminal pass, pc_has[k] bit 0 / bit 1 = which exist.  Dropped with the configuration. */
+  int pc_n, pc_has[RC_MAX_VIEWS]; RpPointsEntry pc_obs[RC_MAX_VIEWS], pc_fin[RC_MAX_VIEWS];
 };
 
 #define EV_PER_STEP (2 + 2 * (2 * K_NSUB + 2))   /* step pair + a pair per launch (action, 12 prep, 12 solve, obs) */
@@ -142,6 +146,7 @@ static int table_get(rp_sim* h, const float* tab, TabCols<float> c, void* stream
 
 static void image_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s);      /* (beside the render entry points, below) */
 static void views_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s);
+static void points_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s);
 
 static OutPtrs to_ptrs(const rp_out* o) {
   OutPtrs p;
@@ -1113,9 +1118,40 @@ static void views_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_
  * or the ended envs' (final = true: rp_step_autoreset's terminal pass).  Two launches on `s`; nothing is checked, reserved or read back here. */
 static void image_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
   if (!h->io_on || (final && !h->io_final)) return;
-  if (h->io_on == 2) { views_pass(h, final, sel32, sel8, s); return; }
-  if (final) views_launch(h, h->io, 0, h->io_frgb, h->io_fdepth, h->io_fseg, nullptr, nullptr, sel32, sel8, s);
+  if (h->io_on == 2) views_pass(h, final, sel32, sel8, s);
+  else if (final) views_launch(h, h->io, 0, h->io_frgb, h->io_fdepth, h->io_fseg, nullptr, nullptr, sel32, sel8, s);
   else views_launch(h, h->io, 0, h->io_rgb, h->io_depth, h->io_seg, nullptr, nullptr, sel32, sel8, s);
+  if (h->pc_n) points_pass(h, final, sel32, sel8, s);
+}
+
+/* k_point_cloud for `n` table entries over envs [first_env, first_env + num) on `s`, behind the draw that wrote their layers (and rc_ee, which the gripper camera's
+ * basis reads) */
+static void points_launch(rp_sim* h, const RpPointsTable& t, int n, int first_env, int num, const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
+  const bool sel = sel32 || sel8;
+  hipLaunchKernelGGL(sel ? k_point_cloud<true> : k_point_cloud<false>, dim3((unsigned)n * (unsigned)num), dim3(256), 0, s, t, n, num, first_env, (const float*)h->rc_ee,
+                     (const int*)sel32, sel8);
+}
+
+/* rp_set_image_points' launch behind an image pass: ONE k_point_cloud for all views of the pass that have a cloud, with the pass's selection */
+static void points_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
+  RpPointsTable t;
+  int n = 0;
+  for (int k = 0; k < RC_MAX_VIEWS; k++)
+    if (h->pc_has[k] & (final ? 2 : 1)) t.v[n++] = final ? h->pc_fin[k] : h->pc_obs[k];
+  for (int k = n; k < RC_MAX_VIEWS; k++) memset(&t.v[k], 0, sizeof(t.v[k]));
+  if (n) points_launch(h, t, n, 0, h->cfg.num_envs, sel32, sel8, s);
+}
+
+/* every attachment goes with the image configuration it was made on (rp_set_image_obs, rp_set_image_views: replaced or switched off) */
+static void points_drop(rp_sim* h) { h->pc_n = 0; memset(h->pc_has, 0, sizeof(h->pc_has)); }
+
+/* rp_points_spec's own rules: the complaint, or null */
+static const char* spec_complaint(const rp_points_spec* spec) {
+  if (!spec) return "spec is NULL";
+  if (spec->max_points < 1 || spec->max_points > 65536) return "max_points lies outside 1 .. 65536";
+  if (spec->frame != RP_POINTS_WORLD && spec->frame != RP_POINTS_CAMERA) return "unknown frame";
+  if (!(spec->max_depth == spec->max_depth)) return "max_depth is not a number";
+  return nullptr;
 }
 
 /* the one path behind rp_render_ex and rp_render_layers: views_check, the pose table for the call's envs, views_launch on `stream` */
@@ -1155,6 +1191,7 @@ int rp_set_image_obs(rp_handle h, const rp_camera* cam, const float* cam_rows, f
   if (width == 0 && height == 0) {
     if (h->io_on) HIPCHK(h, hipDeviceSynchronize());
     h->io_on = 0; h->io_final = 0;
+    points_drop(h);
     return RP_OK;
   }
   const char* bad = layers_complaint(cam, cam_rows, near_plane, far_plane, depth_mode, rgb, depth, segmentation);
@@ -1163,6 +1200,7 @@ int rp_set_image_obs(rp_handle h, const rp_camera* cam, const float* cam_rows, f
   int rc = views_check(h, "rp_set_image_obs", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, 0, h->cfg.num_envs, nullptr, &v);
   if (rc != RP_OK) return rc;
   if (h->io_on) HIPCHK(h, hipDeviceSynchronize());
+  points_drop(h);      /* rp_set_image_points' clouds go with the configuration they were attached to */
   rc = rc_reserve(h, h->cfg.num_envs);
   if (rc != RP_OK) { h->io_on = 0; h->io_final = 0; return rc; }      /* (the table it had may be gone) */
   h->io = v;
@@ -1185,6 +1223,7 @@ int rp_set_image_views(rp_handle h, const rp_image_view* views, int32_t n_views)
   RpViewTable obs, fin;
   memset(&obs, 0, sizeof(obs)); memset(&fin, 0, sizeof(fin));
   int nf = 0; long long tiles = 0, ftiles = 0;
+  int fmap[RC_MAX_VIEWS] = {-1, -1, -1, -1};
   for (int k = 0; k < n_views; k++) {
     const rp_image_view& w = views[k];
     char who[48];
@@ -1204,6 +1243,7 @@ int rp_set_image_views(rp_handle h, const rp_image_view* views, int32_t n_views)
     tiles += e.tiles;
     if (w.final_rgb || w.final_depth || w.final_segmentation) {
       e.tile0 = (int)ftiles; e.rgb = w.final_rgb; e.depth = w.final_depth; e.seg = w.final_segmentation;
+      fmap[k] = nf;
       fin.v[nf++] = e;
       ftiles += e.tiles;
     }
@@ -1216,8 +1256,10 @@ int rp_set_image_views(rp_handle h, const rp_image_view* views, int32_t n_views)
   }
   DevGuard guard(h->cfg.device);
   if (h->io_on) HIPCHK(h, hipDeviceSynchronize());
+  points_drop(h);
   int rc = rc_reserve(h, N);
   if (rc != RP_OK) { h->io_on = 0; h->io_final = 0; return rc; }      /* (the table it had may be gone) */
+  for (int k = 0; k < RC_MAX_VIEWS; k++) h->iv_fmap[k] = fmap[k];
   h->iv_obs = obs; h->iv_fin = fin; h->iv_n = n_views; h->iv_fn = nf; h->iv_tiles = (int)tiles; h->iv_ftiles = (int)ftiles;
   h->io_final = nf > 0 ? 1 : 0;
   h->io_on = 2;
@@ -1247,6 +1289,90 @@ int rp_render_layers(rp_handle h, const rp_camera* cam, const float* cam_rows, f
   if (bad) { snprintf(h->err, 256, "rp_render_layers: %s", bad); return RP_ERR_ARG; }
   return render_views(h, "rp_render_layers", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, first_env, num_envs, rgb, depth,
                       segmentation, sub_goal, ghost_arm, stream);
+}
+
+/* one table entry: the view's camera and size, the layers to read, the outputs, the spec */
+static RpPointsEntry points_entry(const RpCamera& cam, const float* cam_rows, int width, int height, const uint8_t* rgb, const float* depth, const int32_t* seg,
+                                  const rp_points_spec* spec, float* xyz, int32_t* point_seg, uint8_t* point_rgb, int32_t* count) {
+  RpPointsEntry e;
+  memset(&e, 0, sizeof(e));
+  e.cam = cam; e.cam_rows = cam_rows; e.width = width; e.height = height;
+  e.depth = depth; e.seg = seg; e.rgb = point_rgb ? rgb : nullptr;
+  e.xyz = xyz; e.pseg = point_seg; e.prgb = point_rgb; e.count = count;
+  e.max_points = spec->max_points; e.frame = spec->frame; e.max_depth = spec->max_depth; e.drop = spec->drop;
+  return e;
+}
+
+/* Point clouds behind a draw of its own: k_collider_poses, k_render_layers (metres, near 0.01, far 10, no ghosts, the handle's visuals) into the caller's layer
+ * buffers, k_point_cloud - three launches on `stream`, nothing read back. */
+int rp_render_points(rp_handle h, const rp_camera* cam, const float* cam_rows, int32_t width, int32_t height, int32_t first_env, int32_t num_envs,
+                     const rp_points_spec* spec, uint8_t* rgb, float* depth, int32_t* segmentation, float* xyz, int32_t* point_seg, uint8_t* point_rgb,
+                     int32_t* count, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  const char* bad = spec_complaint(spec);
+  if (!bad && (!depth || !segmentation)) bad = "the depth and segmentation layer buffers are both required";
+  if (!bad && !xyz && !count) bad = "no output (xyz and count are both NULL)";
+  if (!bad && point_rgb && !rgb) bad = "point_rgb needs the rgb layer buffer";
+  if (!bad) bad = layers_complaint(cam, cam_rows, 0.01f, 10.f, RP_DEPTH_METRES, rgb, depth, segmentation);
+  if (bad) { snprintf(h->err, 256, "rp_render_points: %s", bad); return RP_ERR_ARG; }
+  RpViews v;
+  int rc = views_check(h, "rp_render_points", cam, cam_rows, 0.01f, 10.f, 1, width, height, first_env, num_envs, nullptr, &v);
+  if (rc != RP_OK) return rc;
+  DevGuard guard(h->cfg.device);
+  rc = rc_reserve(h, num_envs);
+  if (rc != RP_OK) return rc;
+  h->rc_last_num = num_envs;
+  views_launch(h, v, first_env, rgb, depth, segmentation, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  RpPointsTable t;
+  memset(&t, 0, sizeof(t));
+  t.v[0] = points_entry(v.cam, v.cam_rows, width, height, rgb, depth, segmentation, spec, xyz, point_seg, point_rgb, count);
+  points_launch(h, t, 1, first_env, num_envs, nullptr, nullptr, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+/* A cloud on view `view` of the image configuration in force: every check is made here, a stepping call only launches (points_pass).  A refusal leaves the
+ * attachments as they were. */
+int rp_set_image_points(rp_handle h, int32_t view, const rp_points_spec* spec, float* xyz, int32_t* point_seg, uint8_t* point_rgb, int32_t* count, float* final_xyz,
+                        int32_t* final_point_seg, uint8_t* final_point_rgb, int32_t* final_count) {
+  if (!h) return RP_ERR_ARG;
+  if (!h->io_on) { snprintf(h->err, 256, "rp_set_image_points: no image configuration is in force (rp_set_image_obs or rp_set_image_views first)"); return RP_ERR_ARG; }
+  const int nv = h->io_on == 2 ? h->iv_n : 1;
+  if (view < 0 || view >= nv) { snprintf(h->err, 256, "rp_set_image_points: view %d lies outside 0 .. %d", view, nv - 1); return RP_ERR_ARG; }
+  DevGuard guard(h->cfg.device);
+  if (!spec) {      /* detach: calls in flight may still write the old outputs */
+    if (h->pc_has[view]) { HIPCHK(h, hipDeviceSynchronize()); h->pc_has[view] = 0; h->pc_n--; }
+    return RP_OK;
+  }
+  /* the view's layers, observation and terminal, and its camera */
+  RpCamera cam; const float* cam_rows; int width, height, metres;
+  const uint8_t *rgb, *frgb = nullptr; const float *depth, *fdepth = nullptr; const int32_t *seg, *fseg = nullptr;
+  if (h->io_on == 2) {
+    const RpViewEntry& e = h->iv_obs.v[view];
+    cam = e.cam; cam_rows = e.cam_rows; width = e.width; height = e.height; metres = e.metres; rgb = e.rgb; depth = e.depth; seg = e.seg;
+    if (h->iv_fmap[view] >= 0) { const RpViewEntry& f = h->iv_fin.v[h->iv_fmap[view]]; frgb = f.rgb; fdepth = f.depth; fseg = f.seg; }
+  } else {
+    cam = h->io.cam; cam_rows = h->io.cam_rows; width = h->io.width; height = h->io.height; metres = h->io.metres;
+    rgb = h->io_rgb; depth = h->io_depth; seg = h->io_seg; frgb = h->io_frgb; fdepth = h->io_fdepth; fseg = h->io_fseg;
+  }
+  const bool fin = final_xyz || final_point_seg || final_point_rgb || final_count;
+  const char* bad = spec_complaint(spec);
+  if (!bad && (!depth || !metres)) bad = "the view has no depth layer in RP_DEPTH_METRES";
+  if (!bad && !seg) bad = "the view has no segmentation layer";
+  if (!bad && !xyz && !count) bad = "no output (xyz and count are both NULL)";
+  if (!bad && point_rgb && !rgb) bad = "point_rgb is given but the view has no rgb layer";
+  if (!bad && fin && (!fdepth || !fseg)) bad = "a final_* output is given but the view has no final depth and segmentation layers";
+  if (!bad && final_point_rgb && !frgb) bad = "final_point_rgb is given but the view has no final rgb layer";
+  if (bad) { snprintf(h->err, 256, "rp_set_image_points: view %d: %s", view, bad); return RP_ERR_ARG; }
+  if (h->pc_has[view]) HIPCHK(h, hipDeviceSynchronize());      /* replaced: as above */
+  else h->pc_n++;
+  h->pc_obs[view] = points_entry(cam, cam_rows, width, height, rgb, depth, seg, spec, xyz, point_seg, point_rgb, count);
+  h->pc_has[view] = 1;
+  if (fin) {
+    h->pc_fin[view] = points_entry(cam, cam_rows, width, height, frgb, fdepth, fseg, spec, final_xyz, final_point_seg, final_point_rgb, final_count);
+    h->pc_has[view] |= 2;
+  }
+  return RP_OK;
 }
 
 /* test seam and benchmark control: on = 0 puts every record on every tile's shortlist (the default is on) */

@@ -14,6 +14,8 @@
  *                      cameras (rp_render, rp_render_ex: the colour alone; rp_render_layers)
  *   k_render_views     the tiles of up to four views of the same envs in one launch, behind one k_collider_poses (rp_set_image_views)
  *                      all three as <SEL = true> too: the envs a device array selects (rp_set_image_obs: the ended envs' terminal frames, a masked reset's images)
+ *   k_point_cloud      behind a draw: the hits of an env's depth + segmentation layers compacted in scan order into a fixed number of points, evenly subsampled
+ *                      (rp_render_points, rp_set_image_points); <SEL = true> as above
  *   k_ray_test         K rays per env against the same table: hit fraction, position, normal, collider, Bullet link index */
 #pragma once
 
@@ -230,6 +232,34 @@ __device__ __forceinline__ void rc_gripper_basis(const M3& R, V3& fwd, V3& right
   up = cross(right, fwd);
 }
 
+/* the view of env slot `slot` of a launch into V[0 .. 13] = eye, fwd, right, up, tan_half_fov, aspect (one thread; V in LDS): from the env's row of cam_rows with
+ * device_camera's operations (rp_playroom.hip) in double, else from the launch's RpCamera, for the gripper camera (mode 1) at the env's EE pose.  rc_draw_tile and
+ * k_point_cloud both build their view here, so a point is unprojected along the very ray its pixel was cast along. */
+__device__ __forceinline__ void rc_view_basis(const RpCamera& cam, const float* __restrict__ cam_rows, const float* __restrict__ ee_pose, int slot, float* V) {
+  if (cam_rows) {      /* device_camera (rp_playroom.hip), operation by operation */
+    const float* c = cam_rows + 11 * (size_t)slot;
+    double f[3], u[3], s[3], nn = 0;
+    for (int k = 0; k < 3; k++) { f[k] = c[3 + k] - c[k]; nn += f[k] * f[k]; }
+    nn = sqrt(nn > 0 ? nn : 1);
+    for (int k = 0; k < 3; k++) f[k] /= nn;
+    s[0] = f[1] * c[8] - f[2] * c[7]; s[1] = f[2] * c[6] - f[0] * c[8]; s[2] = f[0] * c[7] - f[1] * c[6];
+    nn = sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]); nn = nn > 0 ? nn : 1;
+    for (int k = 0; k < 3; k++) s[k] /= nn;
+    u[0] = s[1] * f[2] - s[2] * f[1]; u[1] = s[2] * f[0] - s[0] * f[2]; u[2] = s[0] * f[1] - s[1] * f[0];
+    for (int k = 0; k < 3; k++) { V[k] = c[k]; V[3 + k] = (float)f[k]; V[6 + k] = (float)s[k]; V[9 + k] = (float)u[k]; }
+    V[12] = (float)tan(0.5 * c[9] * 0.01745329251994329547); V[13] = c[10];
+  } else {
+    V3 eye = ld3(cam.eye), fwd = ld3(cam.fwd), right = ld3(cam.right), up = ld3(cam.up);
+    if (cam.mode == 1) {       /* gripper_camera (environments.py:33-49): at the EE link, the reference's basis from the link's Euler angles */
+      const float* e = ee_pose + 12 * slot;
+      eye = ld3(e);
+      rc_gripper_basis(ldm3(e + 3), fwd, right, up);
+    }
+    st3(V, eye); st3(V + 3, fwd); st3(V + 6, right); st3(V + 9, up);
+    V[12] = cam.tan_half_fov; V[13] = cam.aspect;
+  }
+}
+
 /* rp_render, rp_render_ex (obs['img'], environments.py:841-845: the colour alone) and rp_render_layers: colour, depth and segmentation of getCameraImage in one pass, a
  * 16 x 16 pixel tile per block, one thread per pixel, row 0 = top of the image, uint8 rgb.
  *
@@ -265,28 +295,7 @@ __device__ __forceinline__ void rc_draw_tile(const DevModel* __restrict__ m, con
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) {
-    if (cam_rows) {      /* device_camera (rp_playroom.hip), operation by operation */
-      const float* c = cam_rows + 11 * (size_t)slot;
-      double f[3], u[3], s[3], nn = 0;
-      for (int k = 0; k < 3; k++) { f[k] = c[3 + k] - c[k]; nn += f[k] * f[k]; }
-      nn = sqrt(nn > 0 ? nn : 1);
-      for (int k = 0; k < 3; k++) f[k] /= nn;
-      s[0] = f[1] * c[8] - f[2] * c[7]; s[1] = f[2] * c[6] - f[0] * c[8]; s[2] = f[0] * c[7] - f[1] * c[6];
-      nn = sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]); nn = nn > 0 ? nn : 1;
-      for (int k = 0; k < 3; k++) s[k] /= nn;
-      u[0] = s[1] * f[2] - s[2] * f[1]; u[1] = s[2] * f[0] - s[0] * f[2]; u[2] = s[0] * f[1] - s[1] * f[0];
-      for (int k = 0; k < 3; k++) { V[k] = c[k]; V[3 + k] = (float)f[k]; V[6 + k] = (float)s[k]; V[9 + k] = (float)u[k]; }
-      V[12] = (float)tan(0.5 * c[9] * 0.01745329251994329547); V[13] = c[10];
-    } else {
-      V3 eye = ld3(cam.eye), fwd = ld3(cam.fwd), right = ld3(cam.right), up = ld3(cam.up);
-      if (cam.mode == 1) {       /* gripper_camera (environments.py:33-49): at the EE link, the reference's basis from the link's Euler angles */
-        const float* e = ee_pose + 12 * slot;
-        eye = ld3(e);
-        rc_gripper_basis(ldm3(e + 3), fwd, right, up);
-      }
-      st3(V, eye); st3(V + 3, fwd); st3(V + 6, right); st3(V + 9, up);
-      V[12] = cam.tan_half_fov; V[13] = cam.aspect;
-    }
+    rc_view_basis(cam, cam_rows, ee_pose, slot, V);
     if (vis) {
       const float* lb = vis + (size_t)(first + slot) * (3 * m->n_col + VIS_TAIL) + 3 * m->n_col;
       for (int k = 0; k < VIS_TAIL; k++) V[14 + k] = lb[k];
@@ -422,6 +431,117 @@ __global__ void __launch_bounds__(256) k_render_views(const DevModel* __restrict
   const RpViewEntry& e = vt.v[k];
   rc_draw_tile(m, tab, cnt, e.cam, e.cam_rows, ee_pose, e.width, e.height, cull, e.near_plane, e.far_plane, e.metres, e.rgb, e.depth, e.seg, vis, 0, slot, g - e.tile0,
                e.tiles_x);
+}
+
+/* rp_render_points / rp_set_image_points: a fixed-size point cloud per env from the depth (metres) and segmentation layers a draw has just written, one block of four
+ * waves per (env, attached view); up to RC_MAX_VIEWS clouds per launch from a by-value table, the view of a block found block-uniformly (blockIdx.x / num).
+ *
+ * The rule (include/rp_playroom.h; tests/point_cloud_cases.py is its numpy twin): pixels in row-major order i = y width + x; pixel i is VALID iff seg[i] != -1, bit
+ * (seg[i] & 0xFF) of drop is clear and (max_depth <= 0 || depth[i] <= max_depth); n = the valid pixels, r(i) = the rank of a valid pixel among them, P = max_points.
+ * n <= P: slot r(i) takes pixel i, slots n .. P - 1 are padding (xyz 0, seg -1, rgb 0).  n > P: slot j takes the valid pixel of rank floor(j n / P), 64-bit; those ranks
+ * rise strictly with j (n / P > 1), so the thread of rank r decides alone: j0 = ceil(r P / n) is the one slot that can name r, and does iff j0 < P && floor(j0 n / P) == r.
+ * count = n, not capped.
+ *
+ * Two passes over the pixels in chunks of 256, both reading depth / seg coalesced: COUNT (each wave adds up its ballots' popcounts, one LDS word per wave at the end)
+ * and PLACE (rank = the running base of the chunks before + the valid pixels of the lower waves of this chunk, from four LDS words per chunk, double-buffered: one
+ * barrier per chunk + the lower lanes of the own ballot).  No atomics: the order is the scan order, the same on every run.  The same block then writes the padding and
+ * thread 0 the count.  xyz in float32, operation by operation (the build has -ffp-contract=off), in rc_draw_tile's order: nx, ny the pixel's own expressions, z the depth
+ * value; RP_POINTS_CAMERA (nx z, ny z, z) along (right, up, forward) - the third component IS the depth value -, RP_POINTS_WORLD eye + ((fwd + right nx) + up ny) z.
+ *
+ * sel32, sel8: rc_selected by env first + slot; an unselected env's block leaves before it reads or writes anything, ahead of the first barrier.  Every index is
+ * bounded where it is made: a pixel by i < width height, a slot by j < P (n <= P: r < n <= P). */
+struct RpPointsEntry {
+  RpCamera cam; const float* cam_rows;
+  int width, height;
+  const float* depth; const int* seg; const unsigned char* rgb;                 /* the layers [num][height][width] ([...][3]); rgb only for prgb */
+  float* xyz; int* pseg; unsigned char* prgb; int* count;                       /* [num][P][3], [num][P], [num][P][3], [num]; each may be null */
+  int max_points, frame; float max_depth; unsigned long long drop;
+};
+struct RpPointsTable { RpPointsEntry v[RC_MAX_VIEWS]; };
+
+__device__ __forceinline__ bool pc_valid(int sg, float z, float max_depth, unsigned long long drop) {
+  const int c = sg & 0xFF;
+  return sg != -1 && !(c < 64 && ((drop >> c) & 1ull)) && (max_depth <= 0.f || z <= max_depth);
+}
+
+template <bool SEL>
+__global__ void __launch_bounds__(256) k_point_cloud(const RpPointsTable pt, int n_views, int num, int first, const float* __restrict__ ee_pose,
+                                                     const int* __restrict__ sel32, const unsigned char* __restrict__ sel8) {
+  __shared__ float V[14];
+  __shared__ int wtot[2][4];
+  const int k = blockIdx.x / num, slot = blockIdx.x - k * num;
+  if (k >= n_views) return;
+  if (SEL && !rc_selected(sel32, sel8, first + slot)) return;
+  const RpPointsEntry& e = pt.v[k];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int width = e.width, height = e.height, npix = width * height, P = e.max_points;
+  const float max_depth = e.max_depth;
+  const unsigned long long drop = e.drop;
+  const float* __restrict__ depth = e.depth + (size_t)slot * npix;
+  const int* __restrict__ seg = e.seg + (size_t)slot * npix;
+  if (tid == 0) rc_view_basis(e.cam, e.cam_rows, ee_pose, slot, V);
+  /* COUNT */
+  int mine = 0;
+  for (int base = 0; base < npix; base += 256) {
+    const int i = base + tid;
+    const bool ok = i < npix && pc_valid(seg[i], depth[i], max_depth, drop);
+    mine += __popcll(__ballot(ok));
+  }
+  if (lane == 0) wtot[0][wave] = mine;
+  __syncthreads();                                       /* (the view is in V from here on, too) */
+  const int n = wtot[0][0] + wtot[0][1] + wtot[0][2] + wtot[0][3];
+  __syncthreads();
+  const V3 eye = ld3(V), fwd = ld3(V + 3), right = ld3(V + 6), up = ld3(V + 9);
+  const float thf = V[12], aspect = V[13];
+  float* __restrict__ xyz = e.xyz ? e.xyz + (size_t)slot * P * 3 : nullptr;
+  int* __restrict__ pseg = e.pseg ? e.pseg + (size_t)slot * P : nullptr;
+  unsigned char* __restrict__ prgb = e.prgb ? e.prgb + (size_t)slot * P * 3 : nullptr;
+  const unsigned char* __restrict__ rgb = e.rgb ? e.rgb + (size_t)slot * npix * 3 : nullptr;
+  /* PLACE */
+  int run = 0, buf = 0;
+  for (int base = 0; base < npix; base += 256, buf ^= 1) {
+    const int i = base + tid;
+    int sg = -1; float z = 0.f;
+    if (i < npix) { sg = seg[i]; z = depth[i]; }
+    const bool ok = i < npix && pc_valid(sg, z, max_depth, drop);
+    const unsigned long long bal = __ballot(ok);
+    if (lane == 0) wtot[buf][wave] = __popcll(bal);
+    __syncthreads();                                     /* one barrier per chunk: the next chunk writes the other buffer, and the one after it comes behind the next barrier */
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) { const int c = wtot[buf][w]; before += w < wave ? c : 0; all += c; }
+    if (ok) {
+      const int r = run + before + __popcll(bal & ((1ull << lane) - 1ull));
+      long long j = r;
+      bool take = true;
+      if (n > P) {
+        j = ((long long)r * P + n - 1) / n;
+        take = j < P && (j * n) / P == r;
+      }
+      if (take && j < P) {
+        if (xyz) {
+          const int y = i / width, x = i - y * width;
+          const float nx = (2.f * (x + 0.5f) / width - 1.f) * thf * aspect, ny = (1.f - 2.f * (y + 0.5f) / height) * thf;
+          float* o = xyz + 3 * (size_t)j;
+          if (e.frame == 1) { o[0] = nx * z; o[1] = ny * z; o[2] = z; }
+          else {
+            o[0] = eye.x + ((fwd.x + right.x * nx) + up.x * ny) * z;
+            o[1] = eye.y + ((fwd.y + right.y * nx) + up.y * ny) * z;
+            o[2] = eye.z + ((fwd.z + right.z * nx) + up.z * ny) * z;
+          }
+        }
+        if (pseg) pseg[j] = sg;
+        if (prgb) { const unsigned char* c = rgb + 3 * (size_t)i; unsigned char* o = prgb + 3 * (size_t)j; o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; }
+      }
+    }
+    run += all;
+  }
+  for (int j = n + tid; j < P; j += 256) {               /* padding (n < P only) */
+    if (xyz) { xyz[3 * (size_t)j] = 0.f; xyz[3 * (size_t)j + 1] = 0.f; xyz[3 * (size_t)j + 2] = 0.f; }
+    if (pseg) pseg[j] = -1;
+    if (prgb) { prgb[3 * (size_t)j] = 0; prgb[3 * (size_t)j + 1] = 0; prgb[3 * (size_t)j + 2] = 0; }
+  }
+  if (tid == 0 && e.count) e.count[slot] = n;
 }
 
 /* rayTest (environments.py:738-741) for K rays per env: from / to [num][K][3]; fraction 1 and collider -1 on a miss */

@@ -349,6 +349,9 @@ class VecPlayEnv:
         self.image_obs = None               # set_image_obs: {'rgb' / 'depth' / 'segmentation': the tensors step / reset / calc_state write}, owned like buf
         self.image_final = None             # ... and under autoreset the ended envs' last frames (info['terminal_observation'])
         self.image_cameras = None           # ... and its per-env cameras [N, 11], read on the device at every draw: rewrite rows in place
+        self._image_depth = None            # ... and its depth mode ('buffer' / 'metres'; set_image_views: {name: mode}), which set_image_points checks
+        self.image_points = None            # set_image_points on set_image_obs' view: {'xyz', 'segmentation', 'count'[, 'rgb']}, obs['points']
+        self.image_points_final = None      # ... and under autoreset the ended envs' (info['terminal_observation']['points'])
         self.image_views = None             # set_image_views: {name: {layer: tensor}}, obs['views']; the handle has this configuration or set_image_obs', never both
         self.image_views_final = None       # ... under autoreset {name: {layer: tensor}} of the views with terminal frames (info['terminal_observation']['views'])
         self.image_view_cameras = {}        # ... {name: the per-env cameras [N, 11]} of the views that have them: rewrite rows in place
@@ -387,6 +390,8 @@ class VecPlayEnv:
             o['img'] = self.image_views.get('img', {}).get('rgb')
         elif self.image_obs is not None:    # set_image_obs: the library drew them inside the call that wrote buf
             o.update(self._image_keys(self.image_obs))
+            if self.image_points is not None:
+                o['points'] = self.image_points
         elif self.record_images:
             lo, hi = self.image_envs or (0, self.num_envs)
             if self._img is None or self._img.shape[0] != hi - lo:
@@ -472,6 +477,8 @@ class VecPlayEnv:
                 'reset_row': self._reset_row}      # the table row each ended env restarted from, -1 elsewhere (and everywhere without a table)
         if self.image_final is not None:
             info['terminal_observation'].update(self._image_keys(self.image_final))
+            if self.image_points_final is not None:
+                info['terminal_observation']['points'] = self.image_points_final
         if self.image_views_final is not None:
             info['terminal_observation']['views'] = self.image_views_final
         return self._obs(), self.buf['reward'], reason != 0, info
@@ -931,6 +938,77 @@ class VecPlayEnv:
                    _ptr(res.get('segmentation')), _ptr(sub_goal), _ptr(ghost_arm), self._stream())
         return res
 
+    POINTS_KEYS = ('n', 'frame', 'max_depth', 'drop', 'colour')
+
+    def _points_spec(self, who, n, frame='world', max_depth=None, drop=()):
+        """the host-side checks of a cloud's arguments (ValueError) and the rp_points_spec they make: n in 1 .. 65536, frame 'world' or 'camera', max_depth None
+        (no limit) or a positive finite number of metres, drop a list of names from visual_names"""
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= _lib.MAX_POINTS:
+            raise ValueError('%s: the number of points is an int in 1 .. %d, not %r' % (who, _lib.MAX_POINTS, n))
+        if frame not in ('world', 'camera'):
+            raise ValueError("%s: frame is 'world' or 'camera', not %r" % (who, frame))
+        if max_depth is not None:
+            try:
+                ok = 0.0 < float(max_depth) < float('inf')
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError('%s: max_depth is None or a positive finite number of metres, not %r' % (who, max_depth))
+        names = self.visual_names
+        if isinstance(drop, str) or any(d not in names for d in drop):
+            raise ValueError('%s: drop is a list of names from visual_names (%s), not %r' % (who, ', '.join(sorted(set(names))), drop))
+        bits = 0
+        for c, nm in enumerate(names):
+            if nm in drop:
+                bits |= 1 << c
+        return _lib.RpPointsSpec(n, _lib.POINTS_CAMERA if frame == 'camera' else _lib.POINTS_WORLD, float(max_depth) if max_depth is not None else 0.0, bits)
+
+    def _points_of_view(self, who, points, layers, depth):
+        """the `points` key of set_image_obs / of a view of set_image_views: (rp_points_spec, colour) after its checks (ValueError, `who` names the call and the view)"""
+        who = who + ': points'
+        if not hasattr(points, 'keys') or set(points) - set(self.POINTS_KEYS) or 'n' not in points:
+            raise ValueError('%s is a dict with n and optionally %s, not %r' % (who, ', '.join(self.POINTS_KEYS[1:]), points))
+        colour = bool(points.get('colour', False))
+        need = ('depth', 'segmentation') + (('rgb',) if colour else ())
+        if depth != 'metres' or any(k not in layers for k in need):
+            raise ValueError("%s need the layers %s with depth='metres'; the view has %r with depth=%r" % (who, need, layers, depth))
+        return self._points_spec(who, points['n'], points.get('frame', 'world'), points.get('max_depth'), points.get('drop', ())), colour
+
+    def _points_tensors(self, n, P, colour):
+        """the output tensors of a cloud of P points for n envs"""
+        t = {'xyz': torch.zeros((n, P, 3), dtype=torch.float32, device=self.device), 'segmentation': torch.zeros((n, P), dtype=torch.int32, device=self.device),
+             'count': torch.zeros(n, dtype=torch.int32, device=self.device)}
+        if colour:
+            t['rgb'] = torch.zeros((n, P, 3), dtype=torch.uint8, device=self.device)
+        return t
+
+    @staticmethod
+    def _points_ptrs(t):
+        return [_ptr((t or {}).get(k)) for k in ('xyz', 'segmentation', 'rgb', 'count')]
+
+    def render_points(self, width, height, n_points, envs=None, camera=None, cameras=None, frame='world', max_depth=None, drop=(), colour=False):
+        """A fixed-size point cloud per env from one camera view (rp_render_points): the depth (metres) and segmentation layers of render_layers for envs [lo, hi)
+        (default: all) with the same camera arguments, and their hits compacted on the device into P = n_points points, without a host wait.  Returns a dict of device
+        tensors: 'xyz' float32 [n, P, 3], 'segmentation' int32 [n, P] (the pixel's packed value: unpack_segmentation), 'count' int32 [n], 'rgb' uint8 [n, P, 3] only
+        with colour=True, and 'layers', the layers it drew ({'depth', 'segmentation'[, 'rgb']}).
+
+        The rule: pixels in row-major order; a pixel is valid if its ray hit something (segmentation != -1), its collider is not among drop - a list of names from
+        visual_names, e.g. the table or the ground plate - and its depth is <= max_depth (None: no limit).  With n valid pixels: n <= P keeps them all, in scan
+        order, and slots n .. P - 1 are padding (xyz 0, segmentation -1, rgb 0); n > P keeps, in slot j, the valid pixel of rank floor(j n / P): an even,
+        deterministic stride.  count is n itself, not capped: min(count, P) slots are real and count / P is the subsampling ratio.  frame='camera': (x, y, z) along
+        the camera's right, up and forward axes, z the depth value bit for bit; 'world': eye + (forward + right nx + up ny) z with the basis the renderer used - for
+        the gripper camera (camera=self.camera(gripper=True)) the basis at each env's EE link.  Host values are checked (ValueError)."""
+        spec = self._points_spec('render_points', n_points, frame, max_depth, drop)
+        lo, n, _, _ = self._render_args(envs, None, None)
+        width, height = int(width), int(height)
+        layers = ('depth', 'segmentation') + (('rgb',) if colour else ())
+        layers, shapes, cameras = self._layer_args('render_points', n, width, height, layers, 'metres', camera, cameras, 0.01, 10.0)
+        lay = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
+        pts = self._points_tensors(n, spec.max_points, colour)
+        self._call('rp_render_points', C.byref(camera) if camera is not None else None, _ptr(cameras), width, height, lo, n, C.byref(spec), _ptr(lay.get('rgb')),
+                   _ptr(lay['depth']), _ptr(lay['segmentation']), *self._points_ptrs(pts), self._stream())
+        return {**pts, 'layers': lay}
+
     @staticmethod
     def _image_keys(t):
         """the observation's image keys of a set_image_obs tensor dict: 'img' (the rgb tensor, None unless asked for), 'depth' and 'segmentation' where asked for"""
@@ -949,7 +1027,9 @@ class VecPlayEnv:
         (self.cameras(...)), kept as self.image_cameras and read on the device at every draw, so rows may be rewritten in place between calls (a new camera per
         episode: image_cameras[done] = ...).  depth / near / far as render_layers'.  Host values are checked as render_layers checks them (ValueError).  While set,
         record_images' 200 x 200 render is not made.  set_image_obs(None) switches the feature off: obs['img'] is None, or record_images' picture, again.  Switching on,
-        over or off may synchronise the device; the configuration is not part of get_state / set_state / clone_envs."""
+        over or off may synchronise the device; the configuration is not part of get_state / set_state / clone_envs.
+
+        set_image_points(...) afterwards attaches a point cloud to this view: obs['points'].  This call, like set_image_views, drops a cloud attached before."""
         if width is None:
             self._call('rp_set_image_obs', None, None, 0.0, 0.0, 0, 0, 0, None, None, None, None, None, None)
             self._no_images()
@@ -969,13 +1049,59 @@ class VecPlayEnv:
         self._call('rp_set_image_obs', C.byref(camera) if camera is not None else None, _ptr(cameras), float(near), float(far),
                    _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, *ptrs)
         self._no_images()      # (the handle has one image configuration: this call replaced set_image_views' too)
-        self.image_obs, self.image_final, self.image_cameras = obs, final, cameras
+        self.image_obs, self.image_final, self.image_cameras, self._image_depth = obs, final, cameras, depth
         self._kept['rp_set_image_obs'] = (obs, final, cameras)      # (kept until the next set: the library writes and reads them at every draw)
+
+    def set_image_points(self, n, frame='world', max_depth=None, drop=(), colour=False, view=None):
+        """A point cloud of n points per env as part of the observation (rp_set_image_points), attached to the image configuration in force: to set_image_obs' view
+        (view=None), or to the view of set_image_views that `view` names - where the same arguments can be given as that view's points=dict(n=..., frame=...,
+        max_depth=..., drop=..., colour=...).  The view must list 'depth' with depth='metres' and 'segmentation', plus 'rgb' for colour; a ValueError names the view.
+        From now on every call that draws the view compacts its hits by one more launch behind the draw - one launch for all clouds of a pass -, by render_points' rule
+        and with its arguments (drop takes names from visual_names): where an env's view has more valid pixels than points, slot j holds the valid pixel of rank
+        floor(j n / P) (n valid pixels, P points), and otherwise all of them in scan order followed by padding (xyz 0, segmentation -1, rgb 0); count is the
+        number of valid pixels, not capped.  obs['points'] (set_image_obs) or obs['views'][name]['points'] is {'xyz' float32 [N, P, 3], 'segmentation' int32 [N, P], 'count' int32 [N]
+        [, 'rgb' uint8 [N, P, 3]]}, each row what render_points gives for that env at that moment; a masked reset rewrites the masked envs' rows only.  With
+        autoreset=True, and terminal frames on the view, info['terminal_observation'] carries the same keys at the same place for the ended envs' last frame (rows
+        valid where done).  The tensors are owned like buf.  n=None detaches the cloud; any later set_image_obs or set_image_views drops every cloud."""
+        if self.image_views is not None:
+            if view not in self.image_views:
+                raise ValueError('set_image_points: view is one of %s, not %r' % (', '.join(repr(k) for k in self.image_views), view))
+            who, index, obs, final = 'set_image_points: view %r' % (view,), list(self.image_views).index(view), self.image_views[view], (self.image_views_final or {}).get(view)
+            depth = self._image_depth[view]
+        elif self.image_obs is not None:
+            if view is not None:
+                raise ValueError('set_image_points: view names a view of set_image_views; set_image_obs\' view is view=None, not %r' % (view,))
+            who, index, obs, final, depth = 'set_image_points', 0, self.image_obs, self.image_final, self._image_depth
+        else:
+            raise ValueError('set_image_points: no image configuration is in force (set_image_obs or set_image_views first)')
+        if n is None:
+            self._call('rp_set_image_points', index, None, *[None] * 8)
+            self._set_points(view, None, None)
+            return
+        spec, colour = self._points_of_view(who, dict(n=n, frame=frame, max_depth=max_depth, drop=drop, colour=colour), [k for k in obs if k != 'points'], depth)
+        pts = self._points_tensors(self.num_envs, spec.max_points, colour)
+        fpts = self._points_tensors(self.num_envs, spec.max_points, colour) if final is not None else None
+        self._call('rp_set_image_points', index, C.byref(spec), *self._points_ptrs(pts), *self._points_ptrs(fpts))
+        self._set_points(view, pts, fpts)
+
+    def _set_points(self, view, pts, fpts):
+        """the cloud tensors of a view (None: gone) where the observation finds them; the library holds the same pointers"""
+        self._kept.setdefault('rp_set_image_points', {})[view] = (pts, fpts)      # (kept until the configuration goes: the library writes them at every draw)
+        if self.image_views is None:
+            self.image_points, self.image_points_final = pts, fpts
+            return
+        for t, c in ((self.image_views[view], pts), ((self.image_views_final or {}).get(view), fpts)):
+            if t is not None:
+                t.pop('points', None)
+                if c is not None:
+                    t['points'] = c
 
     def _no_images(self):
         """forget the tensors of the image configuration the library has just dropped (set_image_obs' or set_image_views': the handle holds one)"""
         self.image_obs = self.image_final = self.image_cameras = None
+        self.image_points = self.image_points_final = self._image_depth = None
         self.image_views = self.image_views_final = None
+        self._kept.pop('rp_set_image_points', None)
         self.image_view_cameras = {}
         self._kept.pop('rp_set_image_obs', None)
 
@@ -989,7 +1115,11 @@ class VecPlayEnv:
         envs' last frames (rows valid where done); a view given terminal=False has no terminal tensors and is left out of the terminal pass.  Host values are checked
         per view as set_image_obs checks them; a ValueError names the view.  self.image_view_cameras[name] is the per-env camera tensor of a view that has one: rows
         may be rewritten in place between calls.  While set, record_images' 200 x 200 render is not made.  The handle has ONE image configuration: set_image_views
-        replaces set_image_obs' and the reverse; set_image_views(None) and set_image_obs(None) both switch it off."""
+        replaces set_image_obs' and the reverse; set_image_views(None) and set_image_obs(None) both switch it off.
+
+        A view's dict may carry set_image_points' arguments as points=dict(n=..., frame=..., max_depth=..., drop=..., colour=...): obs['views'][name]['points'] is then that view's
+        cloud {'xyz', 'segmentation', 'count'[, 'rgb']}, and with terminal frames info['terminal_observation']['views'][name]['points'] the ended envs'.  All clouds of
+        a pass are compacted by ONE more launch behind the draw.  A view without points has exactly the keys it has without the feature."""
         if views is None:
             self._call('rp_set_image_views', None, 0)
             self._no_images()
@@ -999,7 +1129,8 @@ class VecPlayEnv:
         N = self.num_envs
         arr = (_lib.RpImageView * len(views))()
         obs, final, cams, keep = {}, {}, {}, []
-        defaults = dict(width=84, height=84, layers=('rgb',), camera=None, cameras=None, depth='buffer', near=0.01, far=10.0, terminal=True)
+        defaults = dict(width=84, height=84, layers=('rgb',), camera=None, cameras=None, depth='buffer', near=0.01, far=10.0, terminal=True, points=None)
+        depths = {}
         for i, (name, kw) in enumerate(views.items()):
             who = 'set_image_views: view %r' % (name,)
             if not hasattr(kw, 'keys') or set(kw) - set(defaults):
@@ -1011,6 +1142,9 @@ class VecPlayEnv:
             layers, shapes, cameras = self._layer_args(who, N, width, height, a['layers'], a['depth'], a['camera'], cameras, a['near'], a['far'])
             if not (0 < width <= 4096 and 0 < height <= 4096):
                 raise ValueError('%s: width and height lie in 1 .. 4096, not %d x %d' % (who, width, height))
+            if a['points'] is not None:
+                self._points_of_view(who, a['points'], layers, a['depth'])      # (checked before anything changes; attached below)
+            depths[name] = a['depth']
             obs[name] = {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
             if self.autoreset and a['terminal']:
                 final[name] = {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
@@ -1029,8 +1163,11 @@ class VecPlayEnv:
                     setattr(v, 'final_' + k, final[name][k].data_ptr())
         self._call('rp_set_image_views', arr, len(views))
         self._no_images()
-        self.image_views, self.image_views_final, self.image_view_cameras = obs, (final if self.autoreset else None), cams
+        self.image_views, self.image_views_final, self.image_view_cameras, self._image_depth = obs, (final if self.autoreset else None), cams, depths
         self._kept['rp_set_image_obs'] = (obs, final, cams)      # (the one image configuration's tensors, kept until the next set or switch-off)
+        for name, kw in views.items():
+            if kw.get('points') is not None:
+                self.set_image_points(view=name, **kw['points'])
 
     def ray_test(self, ray_from, ray_to):
         """bullet_client.rayTest for k rays per env: ray_from / ray_to [N, k, 3] (world).  Returns dict(hit_fraction [N, k] (1 = miss),
