@@ -377,6 +377,47 @@ int rp_set_image_points(rp_handle h, int32_t view, const rp_points_spec* spec,
  * index of an arm collider, -1 otherwise), hit_position [N, k, 3], hit_normal [N, k, 3].  A ray that starts inside a shape does not hit it. */
 int rp_ray_test(rp_handle h, const float* from, const float* to, int32_t k, float* hit_fraction, int32_t* collider, int32_t* link,
                 float* hit_position, float* hit_normal, void* stream);
+/* ---- camera images of stored state rows, and goal images -----------------------------------------------------------------------------------------
+ * rp_render_layers for m images of states the handle need not be in: rows of a caller's device buffer in rp_get_state's layout (a replay buffer, a recorded
+ * dataset), gathered by an index, each drawn with a named row of the handle's visuals table; and, with a goal in RP_GOAL_SOLID, the scene AT the goal.
+ * IMAGE i (row i of rgb [m, height, width, 3] uint8, depth [m, height, width] float, segmentation [m, height, width] int32; each may be NULL, not all three) is byte
+ * for byte what rp_render_layers(h, cam, cam_rows, near_plane, far_plane, depth_mode, width, height, e, 1, ...) writes for an env e whose state record is row
+ * row_index[i] of src->rows and whose visuals row is that of env vis_env[i]: the same cam (NULL = rp_default_camera; mode 1, the gripper camera, sits at the EE
+ * link OF THE ROW'S STATE) or row i of cam_rows (device [m, 11], rp_render_layers' layout; never both), the same near / far / depth mode / size; the toggles' red /
+ * white follow the row's joint values, as on a live env.  Kernels k_collider_poses_rows and k_render_states: k_collider_poses' body and k_render_layers' tile.
+ * THE HANDLE'S OWN STATE: the call never writes the handle's state rows, its contact cache, its counters or any table; a handle that is stepping is afterwards as
+ * it was.  src->rows NULL draws the handle's live rows (row_stride and n_rows are then ignored: 512, N).
+ * row_index[i] outside [0, n_rows): image i is NOT DRAWN - its rows of rgb / depth / segmentation keep what they held (rp_copy_envs' convention for a bad src);
+ * the image's blocks leave before they read the row, ahead of their first barrier, and write nothing: a wrong index is an unwritten image, not a fault.
+ * vis_env NULL, an entry outside [0, N), or a handle whose visuals table was never made (no rp_set_visuals / rp_get_visuals so far) give the DEFAULT row: the
+ * baked colours and the default light and background, the arithmetic of a handle without a table.  The call does not make the table.
+ * goal (device [m, dims.achieved_goal] or NULL), row i for image i.  RP_GOAL_GHOST: rp_render_layers' sub_goal, unchanged - half-transparent ghosts that tint rgb
+ * only; there is no ghost arm in this call.  RP_GOAL_SOLID: the words a sub-goal overwrites for its ghost pass - the objects' positions, and their quaternions on
+ * ids whose goal holds them; on play ids the drawer's y and the scene joints (door, button, dial) - are overwritten for the ONE and only pass: the image is that of
+ * the row with those words replaced, opaque, present in depth and segmentation, the toggles coloured by the GOAL's joint values, no ghost records.  An id without
+ * objects (UR5Reach-v0, the Panda reach ids) has nothing to move: the image is the plain one, as the ghost pass is a no-op there.
+ * CHUNKS: 1 <= m <= 2^31 - 1, not bound to N.  The images are drawn in chunks of at most min(m, max(N, 4096)) pose-table slots, fewer where the chunk's tiles
+ * chunk * ceil(width / 16) * ceil(height / 16) would exceed one launch; each chunk is two launches (poses, draw) on `stream`, the draw in k_render_layers'
+ * tile-major block numbering.  No host wait, no host read of device values; the only allocation is the growth of the pose table to the chunk size at the first call
+ * that needs it.  Shares the handle's ONE collider-pose table with every other call that draws and with rp_ray_test: do not overlap it with such a call on another
+ * stream.
+ * RP_ERR_ARG (nothing is launched; the message names the cause): src NULL; m < 1; rows non-NULL with row_stride < 512, a row_stride that is not a multiple of 4
+ * or n_rows < 1; row_index NULL with m > n_rows (m > N for live rows); all three outputs NULL; both cam and cam_rows; an unknown goal_mode; rp_render_layers' size,
+ * camera, near / far and depth-mode errors. */
+enum rp_goal_mode { RP_GOAL_GHOST = 0, RP_GOAL_SOLID = 1 };
+typedef struct rp_state_rows {
+  const void*    rows;       /* device; rows in rp_get_state's layout.  Only the first 512 bytes of a row (the state record) are read.
+                                NULL = the handle's own live state rows (then row_stride and n_rows are ignored: 512, N) */
+  size_t         row_stride; /* bytes from one row to the next: >= 512 and a multiple of 4 */
+  int32_t        n_rows;     /* rows in the buffer */
+  const int32_t* row_index;  /* device [m] or NULL: image i draws row row_index[i]; NULL: row i (then m <= n_rows) */
+  const int32_t* vis_env;    /* device [m] or NULL: image i is drawn with the visuals row of the handle's env vis_env[i] */
+} rp_state_rows;
+int rp_render_states(rp_handle h, const rp_state_rows* src, int32_t m,
+                     const rp_camera* cam, const float* cam_rows /* device [m, 11] or NULL */,
+                     float near_plane, float far_plane, int32_t depth_mode, int32_t width, int32_t height,
+                     uint8_t* rgb, float* depth, int32_t* segmentation,       /* [m, h, w, 3] / [m, h, w] / [m, h, w]; each may be NULL, not all three */
+                     const float* goal /* device [m, dims.achieved_goal] or NULL */, int32_t goal_mode, void* stream);
 
 /* ---- episodes ended on the device (0.5) ---------------------------------------------------------------------------------------------
  * rp_step_autoreset steps every env as rp_step does (whatever rp_set_fused / rp_set_groups chose) and then resets the envs whose episode ended,

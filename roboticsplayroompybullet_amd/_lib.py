@@ -94,6 +94,16 @@ POINTS_WORLD, POINTS_CAMERA = 0, 1
 MAX_POINTS = 65536       # rp_points_spec.max_points' upper limit
 
 
+class RpStateRows(C.Structure):
+    """rp_state_rows (include/rp_playroom.h): where rp_render_states takes its state rows, which row and which visuals row each image draws"""
+    _fields_ = [('rows', C.c_void_p), ('row_stride', C.c_size_t), ('n_rows', C.c_int32), ('row_index', C.c_void_p), ('vis_env', C.c_void_p)]
+
+
+# rp_goal_mode (include/rp_playroom.h)
+GOAL_GHOST, GOAL_SOLID = 0, 1
+STATE_RECORD_BYTES = 512     # the state record: what rp_render_states reads of a row
+
+
 class RpTimers(C.Structure):
     _fields_ = [('last_step_ms', C.c_float), ('last_reset_ms', C.c_float), ('steps', C.c_uint64), ('steps_timed', C.c_uint32),
                 ('avg_step_ms', C.c_float), ('avg_action_ms', C.c_float), ('avg_prep_ms', C.c_float), ('avg_solve_ms', C.c_float),
@@ -107,10 +117,11 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench',
            'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs',
            'rp_get_visuals_dims', 'rp_set_visuals', 'rp_get_visuals', 'rp_set_image_obs', 'rp_set_image_views',
-           'rp_render_points', 'rp_set_image_points']
+           'rp_render_points', 'rp_set_image_points', 'rp_render_states']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
-                 'rp_debug_autoreset_shape', 'rp_debug_action', 'rp_debug_render_cull', 'rp_debug_image_views_merge']
+                 'rp_debug_autoreset_shape', 'rp_debug_action', 'rp_debug_render_cull', 'rp_debug_image_views_merge',
+                 'rp_debug_render_states_chunk']
 
 _lib = None
 _libs = {}
@@ -183,6 +194,8 @@ def load(wide=False):
     lib.rp_set_image_views.argtypes = [vp, C.POINTER(RpImageView), C.c_int32]
     lib.rp_render_points.argtypes = [vp, C.POINTER(RpCamera), vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RpPointsSpec), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rp_set_image_points.argtypes = [vp, C.c_int32, C.POINTER(RpPointsSpec), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rp_render_states.argtypes = [vp, C.POINTER(RpStateRows), C.c_int32, C.POINTER(RpCamera), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp,
+                                     vp, C.c_int32, vp]
     lib.rp_ray_test.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.rp_debug_substep.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
     lib.rp_set_fused.argtypes = [vp, C.c_int32]
@@ -195,6 +208,7 @@ def load(wide=False):
     lib.rp_debug_action.argtypes = [vp, vp, vp]
     lib.rp_debug_render_cull.argtypes = [vp, C.c_int32]
     lib.rp_debug_image_views_merge.argtypes = [vp, C.c_int32]
+    lib.rp_debug_render_states_chunk.argtypes = [vp, C.c_int32]
     _libs[path] = lib
     if not wide:
         _lib = lib

@@ -66,6 +66,7 @@ struct rp_sim {
   int reset_rounds;        /* rounds the latest rp_reset took (rp_debug) */
   float* rc_tab; int* rc_cnt; float* rc_ee; int rc_cap; int rc_last_num;      /* rp_render / rp_ray_test: collider poses of rc_cap envs (allocated on first use) */
   int render_nocull;       /* rp_debug_render_cull(h, 0): k_render_layers lists every record for every tile (rp_render, rp_render_ex, rp_render_layers) */
+  int rs_chunk;            /* rp_debug_render_states_chunk(h, slots): rp_render_states' chunks hold at most this many images (0: max(N, 4096)) */
   /* rp_set_image_obs: the views of all N envs (io_on = 0: none), the caller's output arrays and the ended envs' (rp_step_autoreset's terminal pass; io_final = any of them) */
   int io_on, io_final; RpViews io;
   uint8_t* io_rgb; float* io_depth; int32_t* io_seg; uint8_t* io_frgb; float* io_fdepth; int32_t* io_fseg;
@@ -1289,6 +1290,63 @@ int rp_render_layers(rp_handle h, const rp_camera* cam, const float* cam_rows, f
   if (bad) { snprintf(h->err, 256, "rp_render_layers: %s", bad); return RP_ERR_ARG; }
   return render_views(h, "rp_render_layers", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, first_env, num_envs, rgb, depth,
                       segmentation, sub_goal, ghost_arm, stream);
+}
+
+/* Images of state rows that need not be the handle's own: per chunk of images k_collider_poses_rows and k_render_states on `stream`, every pointer moved to the chunk's
+ * first image on the host.  A chunk holds min(m, max(N, 4096)) images (rp_debug_render_states_chunk: a test's cap), fewer where its tiles would exceed one launch.
+ * Only the pose table is written (and grown, by rc_reserve, to the chunk size): h->state is read where src->rows is NULL and nothing else of the handle is touched. */
+int rp_render_states(rp_handle h, const rp_state_rows* src, int32_t m, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane,
+                     int32_t depth_mode, int32_t width, int32_t height, uint8_t* rgb, float* depth, int32_t* segmentation, const float* goal, int32_t goal_mode,
+                     void* stream) {
+  if (!h) return RP_ERR_ARG;
+  const int N = h->cfg.num_envs;
+  const char* bad = nullptr;
+  if (!src) bad = "src is NULL";
+  else if (m < 1) bad = "m < 1";
+  else if (src->rows && src->row_stride < RP_REC_FLOATS * sizeof(float)) bad = "row_stride < 512";
+  else if (src->rows && src->row_stride % 4 != 0) bad = "row_stride is not a multiple of 4";
+  else if (src->rows && src->n_rows < 1) bad = "n_rows < 1";
+  else if (!src->row_index && m > (src->rows ? src->n_rows : N)) bad = src->rows ? "m exceeds n_rows and row_index is NULL" : "m exceeds the handle's envs and row_index is NULL (live rows)";
+  else if (goal_mode != RP_GOAL_GHOST && goal_mode != RP_GOAL_SOLID) bad = "unknown goal_mode";
+  if (!bad) bad = layers_complaint(cam, cam_rows, near_plane, far_plane, depth_mode, rgb, depth, segmentation);
+  if (bad) { snprintf(h->err, 256, "rp_render_states: %s", bad); return RP_ERR_ARG; }
+  RpViews v;
+  int rc = views_check(h, "rp_render_states", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, 0, 1, nullptr, &v);
+  if (rc != RP_OK) return rc;
+  const float* rows = src->rows ? (const float*)src->rows : h->state;
+  const size_t row_floats = src->rows ? src->row_stride / sizeof(float) : (size_t)RP_REC_FLOATS;
+  const int n_rows = src->rows ? src->n_rows : N;
+  const long long tiles = (long long)((width + 15) / 16) * ((height + 15) / 16);       /* <= 65536: a chunk never falls below 32767 images */
+  long long cap = h->rs_chunk > 0 ? h->rs_chunk : (N > 4096 ? N : 4096);
+  if (cap > m) cap = m;
+  if (cap * tiles > 0x7fffffffLL) cap = 0x7fffffffLL / tiles;
+  DevGuard guard(h->cfg.device);
+  rc = rc_reserve(h, (int)cap);
+  if (rc != RP_OK) return rc;
+  const size_t npix = (size_t)width * height;
+  const int n_ag = h->host_model.n_ag, cull = h->render_nocull ? 0 : 1;
+  hipStream_t s = (hipStream_t)stream;
+  for (long long base = 0; base < m; base += cap) {
+    const int num = (int)(m - base < cap ? m - base : cap);
+    const int* idx = src->row_index ? src->row_index + base : nullptr;
+    const int* ve = src->vis_env ? src->vis_env + base : nullptr;
+    const float* g = goal ? goal + (size_t)base * n_ag : nullptr;
+    hipLaunchKernelGGL(goal_mode == RP_GOAL_SOLID ? k_collider_poses_rows<true> : k_collider_poses_rows<false>, dim3(num), dim3(64), 0, s, h->dev_model, rows, row_floats,
+                       n_rows, idx, (int)base, num, h->rc_tab, h->rc_cnt, g, h->rc_ee, (const float*)h->vis, ve, N);
+    hipLaunchKernelGGL(k_render_states, dim3((unsigned)(num * tiles)), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, num, v.cam,
+                       cam_rows ? cam_rows + 11 * (size_t)base : nullptr, h->rc_ee, width, height, cull, near_plane, far_plane, v.metres,
+                       rgb ? rgb + 3 * npix * (size_t)base : nullptr, depth ? depth + npix * (size_t)base : nullptr,
+                       segmentation ? segmentation + npix * (size_t)base : nullptr, (const float*)h->vis, ve, N, idx, (int)base, n_rows);
+  }
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+/* test seam: the most images one chunk of rp_render_states holds (0 = the rule: min(m, max(N, 4096))) */
+int rp_debug_render_states_chunk(rp_handle h, int32_t slots) {
+  if (!h || slots < 0) return RP_ERR_ARG;
+  h->rs_chunk = slots;
+  return RP_OK;
 }
 
 /* one table entry: the view's camera and size, the layers to read, the outputs, the spec */

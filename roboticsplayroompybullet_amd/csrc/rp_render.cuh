@@ -14,6 +14,8 @@
  *                      cameras (rp_render, rp_render_ex: the colour alone; rp_render_layers)
  *   k_render_views     the tiles of up to four views of the same envs in one launch, behind one k_collider_poses (rp_set_image_views)
  *                      all three as <SEL = true> too: the envs a device array selects (rp_set_image_obs: the ended envs' terminal frames, a masked reset's images)
+ *   k_collider_poses_rows, k_render_states   the same two for state rows that are not the handle's own: rows of a caller's buffer, gathered by an index, each drawn
+ *                      with a named row of the visuals table, a sub-goal as ghosts or SOLID (rp_render_states)
  *   k_point_cloud      behind a draw: the hits of an env's depth + segmentation layers compacted in scan order into a fixed number of points, evenly subsampled
  *                      (rp_render_points, rp_set_image_points); <SEL = true> as above
  *   k_ray_test         K rays per env against the same table: hit fraction, position, normal, collider, Bullet link index */
@@ -60,86 +62,40 @@ __global__ void __launch_bounds__(64) k_collider_poses(const DevModel* __restric
                                                        float* __restrict__ tab, int* __restrict__ cnt, const float* __restrict__ sub_goal,
                                                        float* __restrict__ ee_pose, const float* __restrict__ ghost_arm, const float* __restrict__ vis,
                                                        const int* __restrict__ sel32, const unsigned char* __restrict__ sel8) {
-  __shared__ EnvLds L;
   const int slot = blockIdx.x, lane = threadIdx.x;
   if (slot >= num) return;
   const int env = first + slot;
   if (SEL && !rc_selected(sel32, sel8, env)) return;      /* block-uniform: the whole wave leaves */
-  load_state(L, state, env, lane);
-  float* out = tab + (size_t)slot * RC_MAX * RC_STRIDE;
-  const bool obj_ghosts = sub_goal && m->num_objects > 0;
-  const int passes = (obj_ghosts || ghost_arm) ? 2 : 1;
-  int nrec = 0;
-  for (int pass = 0; pass < passes; pass++) {
-    if (pass == 1 && ghost_arm) {      /* the ghost arm's joints: rest pose, one IK call, the first six joints (environments.py:575-590 with from_init's pose) */
-      const float* ga = ghost_arm + 8 * (size_t)slot;
-      __syncthreads();
-      if (lane == 0) {
-        const int nrest = m->arm_type == RP_ARM_PANDA ? 8 : 6;
-        for (int i = 0; i < nrest; i++) L.st[ST_Q + i] = m->rest[i];
-      }
-      __syncthreads();
-      ChainQ cur;
-#pragma unroll
-      for (int j = 0; j < 7; j++) cur.q[j] = j < m->ee_chain ? L.st[ST_Q + j] : 0.f;
-      Q4 gq; gq.x = ga[3]; gq.y = ga[4]; gq.z = ga[5]; gq.w = ga[6];
-      const ChainQ sol = ik_solve(m, mk3(ga[0], ga[1], ga[2]), gq, cur, 20, lane & 15);
-      __syncthreads();
-      if (lane == 0) for (int i = 0; i < 6; i++) L.st[ST_Q + i] = sol.q[i];
-      __syncthreads();
-      if (ee_pose && lane < 8) ee_pose[12 * (size_t)num + 8 * (size_t)slot + lane] = L.st[ST_Q + lane];      /* (test hook rp_debug_ghost_joints: the ghost's joints behind the EE poses) */
-    }
-    if (pass == 1 && obj_ghosts) {           /* the sub-goal's poses: objects [pos3 (quat4)] ..., then drawer y, door, button, dial (play ids) */
-      __syncthreads();
-      if (lane == 0) {
-        const float* g = sub_goal + (size_t)slot * m->n_ag;
-        int idx = 0;
-        for (int b = 0; b < m->num_objects; b++) {
-          float* f = &L.st[ST_FREE + 13 * b];
-          for (int k = 0; k < 3; k++) f[k] = g[idx + k];
-          idx += 3;
-          if (m->use_orientation) { for (int k = 0; k < 4; k++) f[3 + k] = g[idx + k]; idx += 4; }
-        }
-        if (m->play) {
-          L.st[ST_FREE + 13 * m->drawer_free + 1] = g[idx];
-          for (int k = 0; k < m->n_j1; k++) L.st[ST_JQ + k] = g[idx + 1 + k];
-        }
-      }
-      __syncthreads();
-    }
-    fk_bodies(m, L, lane);
-    __syncthreads();
-    if (pass == 0 && ee_pose && lane == 0) {        /* EE link pose for the gripper camera */
-      const int eb = m->site_body[RP_SITE_EE];
-      const M3 Rb = ldm3(&L.xR[9 * eb]);
-      const V3 pos = ld3(&L.xp[3 * eb]) + mulv(Rb, ld3(m->site_pos[RP_SITE_EE]));
-      const M3 Rs = mul(Rb, ldm3(m->site_rot[RP_SITE_EE]));
-      float* e = ee_pose + 12 * slot;
-      st3(e, pos);
-      for (int k = 0; k < 9; k++) e[3 + k] = Rs.m[k];
-    }
-    const int cbody = lane < m->n_col ? m->col_body[lane] : 0;
-    const bool mine = lane < m->n_col && (pass == 0 || (obj_ghosts && cbody > m->n_arm) || (ghost_arm && cbody >= 1 && cbody <= m->n_arm));    /* ghosts: free bodies and scene joints of a sub-goal, the arm's links of a ghost arm */
-    const unsigned long long bal = __ballot(mine);
-    if (mine) {
-      const int r = nrec + __popcll(bal & ((1ull << lane) - 1ull));
-      const Xf x = collider_xf(m, L, lane);
-      float* o = out + r * RC_STRIDE;
-      for (int k = 0; k < 9; k++) o[k] = x.R.m[k];
-      st3(o + 9, x.p);
-      st3(o + 12, ld3(m->col_he[lane]));
-      const float* rgb = vis ? vis + (size_t)env * (3 * m->n_col + VIS_TAIL) + 3 * lane : m->col_rgb[lane];
-      float cr = rgb[0], cg = rgb[1], cb = rgb[2];
-      const int tog = m->col_toggle[lane];
-      if (tog == 1 && m->n_j1 > 1) { const bool on = L.st[ST_JQ + 1] < 0.025f; cr = 1.f; cg = on ? 0.f : 1.f; cb = on ? 0.f : 1.f; }
-      if (tog == 2 && m->n_j1 > 2) { const bool on = dial01(L.st[ST_JQ + 2]) < 0.5f; cr = 1.f; cg = on ? 0.f : 1.f; cb = on ? 0.f : 1.f; }
-      o[15] = cr; o[16] = cg; o[17] = cb;
-      o[18] = __int_as_float(m->col_type[lane] | (pass == 1 ? RC_GHOST : 0) | ((m->hpl && m->hpl_cnt[lane] > 0) ? RC_HULL : 0));
-      o[19] = __int_as_float((m->col_link[lane] << 8) | lane);
-    }
-    nrec += __popcll(bal);
-  }
-  if (lane == 0) cnt[slot] = nrec;
+  __shared__ EnvLds L;
+  const int srow = env, venv = env;      /* the env's own state row and its own visuals row */
+  constexpr bool SOLID = false;
+#include "rp_collider_poses_body.inc"
+}
+
+/* rp_render_states: the poses of one chunk of images, slot = the image's place in the chunk.  Image `slot` draws row row_index[slot] of `rows` (row_index null: row
+ * base + slot; the host hands row_index, vis_env and goal in already moved to the chunk's first image) - row_floats floats from one row to the next, the first
+ * RP_REC_FLOATS of a row are the state record - with the colours of row vis_env[slot] of the handle's visuals table `vis`; a null vis or vis_env, or an entry outside
+ * [0, n_envs), gives the baked colours.  A row outside [0, n_rows) is an UNWRITTEN image: the block leaves here, before it reads the row and before any barrier, and
+ * writes nothing (k_render_states makes the same test and never reads this slot of tab / cnt / ee_pose).  goal (may be null): [num][n_ag], k_collider_poses' sub_goal;
+ * SOLID: rp_collider_poses_body.inc.  Nothing but tab / cnt / ee_pose is written: the handle's state is read, at most. */
+template <bool SOLID>
+__global__ void __launch_bounds__(64) k_collider_poses_rows(const DevModel* __restrict__ m, const float* __restrict__ rows, size_t row_floats, int n_rows,
+                                                            const int* __restrict__ row_index, int base, int num, float* __restrict__ tab, int* __restrict__ cnt,
+                                                            const float* __restrict__ goal, float* __restrict__ ee_pose, const float* __restrict__ vis_tab,
+                                                            const int* __restrict__ vis_env, int n_envs) {
+  const int slot = blockIdx.x, lane = threadIdx.x;
+  if (slot >= num) return;
+  const int row = row_index ? row_index[slot] : base + slot;
+  if (row < 0 || row >= n_rows) return;                   /* block-uniform: the whole wave leaves */
+  const int ve = vis_env ? vis_env[slot] : -1;
+  const bool own = vis_tab && ve >= 0 && ve < n_envs;
+  __shared__ EnvLds L;
+  const float* state = rows + (size_t)row * row_floats;      /* the body's names: the record is row 0 from here, no ghost arm, the named visuals row */
+  const float* sub_goal = goal;
+  const float* ghost_arm = nullptr;
+  const float* vis = own ? vis_tab : nullptr;
+  const int srow = 0, venv = own ? ve : 0;
+#include "rp_collider_poses_body.inc"
 }
 
 /* ray o + t d, t in [0, tmax], against a box (R, p, he): entry parameter and the face normal, world frame.  A ray that starts
@@ -399,6 +355,26 @@ __global__ void __launch_bounds__(256) k_render_layers(const DevModel* __restric
   if (tile >= tiles) return;
   if (SEL && !rc_selected(sel32, sel8, first + slot)) return;
   rc_draw_tile(m, tab, cnt, cam, cam_rows, ee_pose, width, height, cull, near_plane, far_plane, metres, rgb, depth, seg, vis, first, slot, tile, tiles_x);
+}
+
+/* rp_render_states: k_render_layers for one chunk of images behind k_collider_poses_rows, the same tile-major block numbering.  The light and the background come from
+ * row vis_env[slot] of the visuals table (a null vis or vis_env, or an entry outside [0, n_envs): the literals, as under a null table); rc_draw_tile reads row
+ * first + slot, so it is handed first = that row - slot, or a null table.  Every tile's block of an unwritten image (k_collider_poses_rows' test of the row) leaves
+ * ahead of the first barrier and the image's rows of rgb / depth / seg keep what they held.  The pixels are rc_draw_tile's: the bytes of k_render_layers. */
+__global__ void __launch_bounds__(256) k_render_states(const DevModel* __restrict__ m, const float* __restrict__ tab, const int* __restrict__ cnt, int num, RpCamera cam,
+                                                       const float* __restrict__ cam_rows, const float* __restrict__ ee_pose, int width, int height, int cull,
+                                                       float near_plane, float far_plane, int metres, unsigned char* __restrict__ rgb, float* __restrict__ depth,
+                                                       int* __restrict__ seg, const float* __restrict__ vis, const int* __restrict__ vis_env, int n_envs,
+                                                       const int* __restrict__ row_index, int base, int n_rows) {
+  const int tiles_x = (width + 15) >> 4, tiles = tiles_x * ((height + 15) >> 4);
+  const int tile = blockIdx.x / num, slot = blockIdx.x - tile * num;
+  if (tile >= tiles) return;
+  const int row = row_index ? row_index[slot] : base + slot;
+  if (row < 0 || row >= n_rows) return;
+  const int ve = vis_env ? vis_env[slot] : -1;
+  const bool own = vis && ve >= 0 && ve < n_envs;
+  rc_draw_tile(m, tab, cnt, cam, cam_rows, ee_pose, width, height, cull, near_plane, far_plane, metres, rgb, depth, seg, own ? vis : nullptr, own ? ve - slot : 0, slot, tile,
+               tiles_x);
 }
 
 /* rp_set_image_views: up to RC_MAX_VIEWS views of the same envs in ONE launch, behind one k_collider_poses (the poses and ee_pose do not depend on the camera).  The

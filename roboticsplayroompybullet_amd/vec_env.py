@@ -1009,6 +1009,73 @@ class VecPlayEnv:
                    _ptr(lay['depth']), _ptr(lay['segmentation']), *self._points_ptrs(pts), self._stream())
         return {**pts, 'layers': lay}
 
+    def render_states(self, states, width, height, index=None, visuals=None, camera=None, cameras=None, layers=('rgb', 'depth', 'segmentation'), depth='buffer',
+                      near=0.01, far=10.0, goal=None, goal_mode='ghost', out=None):
+        """render_layers for M images of states the envs need not be in (rp_render_states): a dict of device tensors 'rgb' uint8 [M, height, width, 3], 'depth'
+        float32 [M, height, width], 'segmentation' int32 [M, height, width].  The live envs are neither written nor disturbed, and M is not bound to num_envs.
+
+        states: a float32 device tensor [R, >= 128] whose last dimension is contiguous - a get_state() result, its [:, :128] slice (the state record is all that is
+        read of a row), a view into a larger replay buffer; the row stride is states.stride(0).  None: the live envs' rows.  index: int32 device tensor [M], image i
+        draws row index[i] (default: row i, M = R); an entry outside [0, R) leaves image i unwritten - its rows of `out` keep what they held.  visuals: None (the
+        default look: baked colours, default light and background) or an int32 device tensor [M] of env indices: image i is drawn with set_visuals' row of env
+        visuals[i]; an entry outside [0, num_envs) gives the default look.  camera / cameras ([M, 11], one row per image), layers, depth, near, far, out: as
+        render_layers'; the gripper camera sits at the EE link of the row's state.
+
+        goal: float32 [M, dims.achieved_goal] or None.  goal_mode='ghost': render_layers' sub_goal - half-transparent ghosts in rgb only.  'solid': the objects
+        and, on play ids, drawer, door, button and dial are drawn AT the goal - opaque, in all three layers, the toggles coloured by the goal's joint values: the
+        image of the row with the goal's words written into it.  Host values are checked (ValueError) before the library is touched; nothing is read back."""
+        who = 'render_states'
+        if states is not None:
+            if not (torch.is_tensor(states) and states.dtype == torch.float32 and states.dim() == 2):
+                raise ValueError('%s: states is None or a float32 tensor [R, >= 128], not %s' % (who, (states.dtype, tuple(states.shape)) if torch.is_tensor(states)
+                                                                                                 else type(states).__name__))
+            if states.shape[0] < 1 or states.shape[1] < 128:
+                raise ValueError('%s: states has at least one row of at least 128 floats (the 512-byte state record), not %s' % (who, tuple(states.shape)))
+            if states.stride(1) != 1 or states.stride(0) < 128:
+                raise ValueError('%s: the last dimension of states is contiguous and its rows lie at least 128 floats apart, not strides %s' % (who, tuple(states.stride())))
+            if not states.is_cuda:
+                raise ValueError('%s: states is a device tensor, not one on %s' % (who, states.device))
+        rows = self.num_envs if states is None else int(states.shape[0])
+        for name, t in (('index', index), ('visuals', visuals)):
+            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 1 and t.is_cuda):
+                raise ValueError('%s: %s is None or an int32 device tensor [M], not %s' % (who, name, (t.dtype, tuple(t.shape), str(t.device)) if torch.is_tensor(t)
+                                                                                           else type(t).__name__))
+        m = rows if index is None else int(index.shape[0])
+        if m < 1:
+            raise ValueError('%s: no image to draw (index is empty)' % who)
+        if visuals is not None and visuals.shape[0] != m:
+            raise ValueError('%s: visuals has %d entries for %d images' % (who, visuals.shape[0], m))
+        if goal_mode not in ('ghost', 'solid'):
+            raise ValueError("%s: goal_mode is 'ghost' or 'solid', not %r" % (who, goal_mode))
+        width, height = int(width), int(height)
+        layers, shapes, cameras = self._layer_args(who, m, width, height, layers, depth, camera, cameras, near, far)
+        if goal is not None:
+            if not (torch.is_tensor(goal) and tuple(goal.shape) == (m, self.dims['achieved_goal'])):
+                raise ValueError('%s: goal is a tensor [%d, %d], not %s' % (who, m, self.dims['achieved_goal'], tuple(goal.shape) if torch.is_tensor(goal) else type(goal).__name__))
+            goal = goal.to(device=self.device, dtype=torch.float32).contiguous()
+        res = {}
+        for k in layers:
+            shape, dtype = shapes[k]
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=self.device)
+            if not (tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.is_cuda):
+                raise ValueError('%s: out[%r] is a contiguous %s device tensor %s, not %s %s' % (who, k, dtype, shape, t.dtype, tuple(t.shape)))
+            res[k] = t
+        index = index.contiguous() if index is not None else None
+        visuals = visuals.contiguous() if visuals is not None else None
+        src = _lib.RpStateRows(_ptr(states), 4 * states.stride(0) if states is not None else 0, rows, _ptr(index), _ptr(visuals))
+        self._call('rp_render_states', C.byref(src), m, C.byref(camera) if camera is not None else None, _ptr(cameras), float(near), float(far),
+                   _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, _ptr(res.get('rgb')), _ptr(res.get('depth')),
+                   _ptr(res.get('segmentation')), _ptr(goal), _lib.GOAL_SOLID if goal_mode == 'solid' else _lib.GOAL_GHOST, self._stream())
+        return res
+
+    def goal_images(self, goal, width, height, camera=None, cameras=None, layers=('rgb', 'depth', 'segmentation'), depth='buffer', near=0.01, far=10.0, out=None):
+        """every live env drawn AT its goal, with its own visuals: render_states(None, width, height, visuals=arange(num_envs), goal=goal, goal_mode='solid', ...) -
+        the goal image a goal-conditioned pixel policy is given.  goal: [num_envs, dims.achieved_goal], e.g. obs['desired_goal']."""
+        return self.render_states(None, width, height, visuals=torch.arange(self.num_envs, dtype=torch.int32, device=self.device), camera=camera, cameras=cameras,
+                                  layers=layers, depth=depth, near=near, far=far, goal=goal, goal_mode='solid', out=out)
+
     @staticmethod
     def _image_keys(t):
         """the observation's image keys of a set_image_obs tensor dict: 'img' (the rgb tensor, None unless asked for), 'depth' and 'segmentation' where asked for"""
