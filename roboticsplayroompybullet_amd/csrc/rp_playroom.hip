@@ -17,12 +17,17 @@
 #include "rp_render.cuh"
 
 
-/* what one draw needs beyond the envs and the output pointers, checked once (views_check): the device camera, or the caller's device rows, the depth mapping, the image
- * size and k_render_layers' grid for `num` envs */
-struct RpViews {
-  RpCamera cam; const float* cam_rows;
-  float near_plane, far_plane; int metres;
-  int width, height, num; unsigned blocks;
+/* a by-value kernel argument (k_render_views' table) and the host's one record of a view: its layout must not move */
+static_assert(sizeof(RpViewEntry) == 128, "RpViewEntry is a by-value kernel argument: its layout must not move");
+
+/* THE image configuration of a handle (image_config_set; n = 0: none): k_render_views' table of the observation pass and that of the terminal pass - the views with a
+ * final_* pointer, with those pointers, n_fin of them -, each with its tile count, and the clouds attached to the views (rp_set_image_points: pc_n = how many views
+ * have one; pc_obs[k] / pc_fin[k] are view k's entries for the two passes, pc_has[k] bit 0 / bit 1 = which exist; dropped with the configuration) */
+struct RpImageConfig {
+  int n, n_fin, tiles, ftiles;
+  RpViewTable obs, fin;
+  int fmap[RC_MAX_VIEWS];         /* view -> its entry of fin, -1: the view has no terminal layers */
+  int pc_n, pc_has[RC_MAX_VIEWS]; RpPointsEntry pc_obs[RC_MAX_VIEWS], pc_fin[RC_MAX_VIEWS];
 };
 
 struct rp_sim {
@@ -67,9 +72,6 @@ struct rp_sim {
   float* rc_tab; int* rc_cnt; float* rc_ee; int rc_cap; int rc_last_num;      /* rp_render / rp_ray_test: collider poses of rc_cap envs (allocated on first use) */
   int render_nocull;       /* rp_debug_render_cull(h, 0): k_render_layers lists every record for every tile (rp_render, rp_render_ex, rp_render_layers) */
   int rs_chunk;            /* rp_debug_render_states_chunk(h, slots): rp_render_states' chunks hold at most this many images (0: max(N, 4096)) */
-  /* rp_set_image_obs: the views of all N envs (io_on = 0: none), the caller's output arrays and the ended envs' (rp_step_autoreset's terminal pass; io_final = any of them) */
-  int io_on, io_final; RpViews io;
-  uint8_t* io_rgb; float* io_depth; int32_t* io_seg; uint8_t* io_frgb; float* io_fdepth; int32_t* io_fseg;
   /* rp_step_autoreset: episode counters [N], the list of ending envs [N], its length and take counter [2], k_autoreset's pairing table [4 * ar_grid] */
   int* ep_steps; int* ar_list; int* ar_ctl; int* ar_pair;
   int ar_grid, ar_epb;     /* k_autoreset's grid (the blocks resident at once; RP_AUTORESET_BLOCKS overrides) and envs per block (RP_AUTORESET_EPB, 1 .. 4, default 1) */
@@ -82,15 +84,8 @@ struct rp_sim {
   float* rt_tab; int rt_rows, rt_n_o; int* rt_cursor; int* rt_env_row; unsigned long long* rt_wave_bal; int* rt_wave_row; int rt_grid;
   rp_timers timers;
   char err[256];
-  /* (behind everything else: the kilobyte of tables moves no older field)
-   * rp_set_image_views with two or more views (io_on = 2; the handle has ONE image configuration, this one or rp_set_image_obs'): k_render_views' table of the observation
-   * pass and that of the terminal pass - the views with a final_* pointer, with those pointers, iv_fn of them -, each with its tile count; built at the set call */
-  RpViewTable iv_obs, iv_fin; int iv_n, iv_fn, iv_tiles, iv_ftiles;
   int iv_nomerge;          /* rp_debug_image_views_merge(h, 0): a k_render_layers launch per view instead of one k_render_views */
-  int iv_fmap[RC_MAX_VIEWS];      /* view -> its entry of iv_fin, -1: the view has no terminal layers */
-  /* rp_set_image_points: the clouds attached to the views of the image configuration in force (pc_n = how many views have one; 0: image_pass launches what it always
-   * launched).  pc_obs[k] / pc_fin[k] are view k's entries for the observation and the terminal pass, pc_has[k] bit 0 / bit 1 = which exist.  Dropped with the configuration. */
-  int pc_n, pc_has[RC_MAX_VIEWS]; RpPointsEntry pc_obs[RC_MAX_VIEWS], pc_fin[RC_MAX_VIEWS];
+  RpImageConfig img;       /* rp_set_image_obs / rp_set_image_views / rp_set_image_points (behind everything else: the kilobytes of tables stand among no other fields) */
 };
 
 #define EV_PER_STEP (2 + 2 * (2 * K_NSUB + 2))   /* step pair + a pair per launch (action, 12 prep, 12 solve, obs) */
@@ -146,7 +141,6 @@ static int table_get(rp_sim* h, const float* tab, TabCols<float> c, void* stream
 }
 
 static void image_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s);      /* (beside the render entry points, below) */
-static void views_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s);
 static void points_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s);
 
 static OutPtrs to_ptrs(const rp_out* o) {
@@ -719,7 +713,7 @@ static int step_impl(rp_handle h, const float* action, const rp_out* out, void* 
 
 int rp_step(rp_handle h, const float* action, const rp_out* out, void* stream) {
   int rc = step_impl(h, action, out, stream);
-  if (rc != RP_OK || !h->io_on) return rc;
+  if (rc != RP_OK || !h->img.n) return rc;
   DevGuard guard(h->cfg.device);
   image_pass(h, false, nullptr, nullptr, (hipStream_t)stream);      /* on the caller's stream, which the group streams have joined */
   HIPCHK(h, hipGetLastError());
@@ -1059,9 +1053,10 @@ static RpCamera device_camera(const rp_camera* c) {
 }
 
 /* the checks of a draw (`who` names the entry point in the messages): the size and range checks, the Panda-only ghost arm, the tile-count limit, the camera (NULL and
- * no cam_rows = the default one); *v is what views_launch needs.  Touches no device. */
+ * no cam_rows = the default one); *e gets the camera, the size with its tile counts and the depth mapping - the outputs and tile0 stay zero for the caller.  Touches
+ * no device. */
 static int views_check(rp_handle h, const char* who, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int metres, int32_t width,
-                       int32_t height, int32_t first_env, int32_t num_envs, const float* ghost_arm, RpViews* v) {
+                       int32_t height, int32_t first_env, int32_t num_envs, const float* ghost_arm, RpViewEntry* e) {
   const char* bad = nullptr;
   if (width <= 0 || height <= 0 || width > 4096 || height > 4096) bad = "bad image size";
   else if (first_env < 0 || num_envs <= 0 || first_env + num_envs > h->cfg.num_envs) bad = "bad env range";
@@ -1072,57 +1067,50 @@ static int views_check(rp_handle h, const char* who, const rp_camera* cam, const
   const long long blocks = (long long)num_envs * ((width + 15) / 16) * ((height + 15) / 16);
   if (blocks > 0x7fffffffLL) { snprintf(h->err, 256, "%s: %lld tiles exceed one launch", who, blocks); return RP_ERR_ARG; }
   rp_camera def;
-  memset(v, 0, sizeof(*v));
+  memset(e, 0, sizeof(*e));
   if (!cam_rows) {
     if (!cam) { rp_default_camera(&def); cam = &def; }
     if (cam->mode < 0 || cam->mode > 1 || !(cam->fov_deg > 0.f && cam->fov_deg < 180.f) || !(cam->aspect > 0.f)) { snprintf(h->err, 256, "%s: bad camera", who); return RP_ERR_ARG; }
-    v->cam = device_camera(cam);
+    e->cam = device_camera(cam);
   }
-  v->cam_rows = cam_rows; v->near_plane = near_plane; v->far_plane = far_plane; v->metres = metres;
-  v->width = width; v->height = height; v->num = num_envs; v->blocks = (unsigned)blocks;
+  e->cam_rows = cam_rows; e->near_plane = near_plane; e->far_plane = far_plane; e->metres = metres;
+  e->width = width; e->height = height; e->tiles_x = (width + 15) / 16; e->tiles = e->tiles_x * ((height + 15) / 16);
   return RP_OK;
 }
 
-/* k_collider_poses and k_render_layers for envs [first_env, first_env + v.num) on `s`, both with the handle's visuals table (nullptr until the first rp_set_visuals /
- * rp_get_visuals) and the selection sel32 / sel8 (rc_selected; indexed by env, so a selection goes with first_env = 0).  The pose table holds v.num envs (rc_reserve). */
-static void views_launch(rp_handle h, const RpViews& v, int first_env, uint8_t* rgb, float* depth, int32_t* segmentation, const float* sub_goal, const float* ghost_arm,
-                         const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
-  const bool sel = sel32 || sel8;      /* the kernels' SEL = true instantiations only where there is a selection: without one they are the kernels they were */
-  hipLaunchKernelGGL(sel ? k_collider_poses<true> : k_collider_poses<false>, dim3(v.num), dim3(64), 0, s, h->dev_model, h->state, first_env, v.num, h->rc_tab, h->rc_cnt,
-                     sub_goal, h->rc_ee, ghost_arm, (const float*)h->vis, (const int*)sel32, sel8);
-  hipLaunchKernelGGL(sel ? k_render_layers<true> : k_render_layers<false>, dim3(v.blocks), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, v.num, v.cam, v.cam_rows,
-                     h->rc_ee, v.width, v.height, h->render_nocull ? 0 : 1, v.near_plane, v.far_plane, v.metres, rgb, depth, segmentation, (const float*)h->vis, first_env,
-                     (const int*)sel32, sel8);
+/* THE k_collider_poses launch: the pose table of envs [first, first + num) on `s` (rc_reserve has made room for num), with the selection sel32 / sel8 (rc_selected;
+ * indexed by env, so a selection goes with first = 0).  The kernels' SEL = true instantiations only where there is a selection: without one they are the kernels they
+ * were.  ee: where the EE poses go (h->rc_ee; null: nobody reads them), vis: the visuals table (h->vis, null until the first rp_set_visuals / rp_get_visuals). */
+static void poses_launch(rp_sim* h, int first, int num, const float* sub_goal, float* ee, const float* ghost_arm, const float* vis, const int32_t* sel32,
+                         const uint8_t* sel8, hipStream_t s) {
+  hipLaunchKernelGGL((sel32 || sel8) ? k_collider_poses<true> : k_collider_poses<false>, dim3(num), dim3(64), 0, s, h->dev_model, h->state, first, num, h->rc_tab, h->rc_cnt,
+                     sub_goal, ee, ghost_arm, vis, (const int*)sel32, sel8);
 }
 
-/* rp_set_image_views' draw (two or more views): ONE k_collider_poses over all N envs - the poses and rc_ee do not depend on the camera - and ONE k_render_views whose
- * grid holds the tiles of every view of the pass; with rp_debug_image_views_merge(h, 0) a k_render_layers launch per view behind the same pose launch.  Same bytes. */
-static void views_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
-  const RpViewTable& t = final ? h->iv_fin : h->iv_obs;
-  const int n = final ? h->iv_fn : h->iv_n, tiles = final ? h->iv_ftiles : h->iv_tiles, N = h->cfg.num_envs, cull = h->render_nocull ? 0 : 1;
-  const bool sel = sel32 || sel8;
-  hipLaunchKernelGGL(sel ? k_collider_poses<true> : k_collider_poses<false>, dim3(N), dim3(64), 0, s, h->dev_model, h->state, 0, N, h->rc_tab, h->rc_cnt, (const float*)nullptr,
-                     h->rc_ee, (const float*)nullptr, (const float*)h->vis, (const int*)sel32, sel8);
-  if (!h->iv_nomerge) {
-    hipLaunchKernelGGL(sel ? k_render_views<true> : k_render_views<false>, dim3((unsigned)N * (unsigned)tiles), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, N, t, n, tiles,
-                       h->rc_ee, cull, (const float*)h->vis, (const int*)sel32, sel8);
-    return;
-  }
-  for (int k = 0; k < n; k++) {
-    const RpViewEntry& e = t.v[k];
-    hipLaunchKernelGGL(sel ? k_render_layers<true> : k_render_layers<false>, dim3((unsigned)N * (unsigned)e.tiles), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, N, e.cam,
-                       e.cam_rows, h->rc_ee, e.width, e.height, cull, e.near_plane, e.far_plane, e.metres, e.rgb, e.depth, e.seg, (const float*)h->vis, 0, (const int*)sel32, sel8);
-  }
+/* THE k_render_layers launch: entry e (views_check, with the caller's outputs) for the `num` envs of the pose table, which are envs [first, first + num) */
+static void layers_launch(rp_sim* h, const RpViewEntry& e, int first, int num, const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
+  hipLaunchKernelGGL((sel32 || sel8) ? k_render_layers<true> : k_render_layers<false>, dim3((unsigned)num * (unsigned)e.tiles), dim3(256), 0, s, h->dev_model, h->rc_tab,
+                     h->rc_cnt, num, e.cam, e.cam_rows, h->rc_ee, e.width, e.height, h->render_nocull ? 0 : 1, e.near_plane, e.far_plane, e.metres, e.rgb, e.depth, e.seg,
+                     (const float*)h->vis, first, (const int*)sel32, sel8);
 }
 
-/* rp_set_image_obs' draw inside a call that writes observation rows: all N envs, or those sel32 / sel8 select on the device, into the observation arrays (final = false)
- * or the ended envs' (final = true: rp_step_autoreset's terminal pass).  Two launches on `s`; nothing is checked, reserved or read back here. */
+/* The image configuration's draw inside a call that writes observation rows: all N envs, or those sel32 / sel8 select on the device, into the observation tensors
+ * (final = false) or the ended envs' (final = true: rp_step_autoreset's terminal pass).  ONE k_collider_poses over all N envs - the poses and rc_ee do not depend on
+ * the camera -, then a configuration of one view draws its entry with k_render_layers and one of several draws the pass's entries with ONE k_render_views, whose grid
+ * holds the tiles of them all (the choice is by the configuration's views, not the pass's); with rp_debug_image_views_merge(h, 0) a k_render_layers launch per entry
+ * instead.  Same bytes.  Nothing is checked, reserved or read back here. */
 static void image_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8_t* sel8, hipStream_t s) {
-  if (!h->io_on || (final && !h->io_final)) return;
-  if (h->io_on == 2) views_pass(h, final, sel32, sel8, s);
-  else if (final) views_launch(h, h->io, 0, h->io_frgb, h->io_fdepth, h->io_fseg, nullptr, nullptr, sel32, sel8, s);
-  else views_launch(h, h->io, 0, h->io_rgb, h->io_depth, h->io_seg, nullptr, nullptr, sel32, sel8, s);
-  if (h->pc_n) points_pass(h, final, sel32, sel8, s);
+  const RpImageConfig& c = h->img;
+  if (!c.n || (final && !c.n_fin)) return;
+  const RpViewTable& t = final ? c.fin : c.obs;
+  const int n = final ? c.n_fin : c.n, tiles = final ? c.ftiles : c.tiles, N = h->cfg.num_envs;
+  poses_launch(h, 0, N, nullptr, h->rc_ee, nullptr, h->vis, sel32, sel8, s);
+  if (c.n == 1 || h->iv_nomerge)
+    for (int k = 0; k < n; k++) layers_launch(h, t.v[k], 0, N, sel32, sel8, s);
+  else
+    hipLaunchKernelGGL((sel32 || sel8) ? k_render_views<true> : k_render_views<false>, dim3((unsigned)N * (unsigned)tiles), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, N,
+                       t, n, tiles, h->rc_ee, h->render_nocull ? 0 : 1, (const float*)h->vis, (const int*)sel32, sel8);
+  if (c.pc_n) points_pass(h, final, sel32, sel8, s);
 }
 
 /* k_point_cloud for `n` table entries over envs [first_env, first_env + num) on `s`, behind the draw that wrote their layers (and rc_ee, which the gripper camera's
@@ -1138,13 +1126,13 @@ static void points_pass(rp_sim* h, bool final, const int32_t* sel32, const uint8
   RpPointsTable t;
   int n = 0;
   for (int k = 0; k < RC_MAX_VIEWS; k++)
-    if (h->pc_has[k] & (final ? 2 : 1)) t.v[n++] = final ? h->pc_fin[k] : h->pc_obs[k];
+    if (h->img.pc_has[k] & (final ? 2 : 1)) t.v[n++] = final ? h->img.pc_fin[k] : h->img.pc_obs[k];
   for (int k = n; k < RC_MAX_VIEWS; k++) memset(&t.v[k], 0, sizeof(t.v[k]));
   if (n) points_launch(h, t, n, 0, h->cfg.num_envs, sel32, sel8, s);
 }
 
 /* every attachment goes with the image configuration it was made on (rp_set_image_obs, rp_set_image_views: replaced or switched off) */
-static void points_drop(rp_sim* h) { h->pc_n = 0; memset(h->pc_has, 0, sizeof(h->pc_has)); }
+static void points_drop(rp_sim* h) { h->img.pc_n = 0; memset(h->img.pc_has, 0, sizeof(h->img.pc_has)); }
 
 /* rp_points_spec's own rules: the complaint, or null */
 static const char* spec_complaint(const rp_points_spec* spec) {
@@ -1155,18 +1143,27 @@ static const char* spec_complaint(const rp_points_spec* spec) {
   return nullptr;
 }
 
-/* the one path behind rp_render_ex and rp_render_layers: views_check, the pose table for the call's envs, views_launch on `stream` */
+/* a draw of an entry point: the pose table for envs [first_env, first_env + num_envs), then entry e (views_check, with the caller's outputs), on `stream` */
+static int entry_draw(rp_handle h, const RpViewEntry& e, int32_t first_env, int32_t num_envs, const float* sub_goal, const float* ghost_arm, void* stream) {
+  int rc = rc_reserve(h, num_envs);
+  if (rc != RP_OK) return rc;
+  h->rc_last_num = num_envs;
+  poses_launch(h, first_env, num_envs, sub_goal, h->rc_ee, ghost_arm, h->vis, nullptr, nullptr, (hipStream_t)stream);
+  layers_launch(h, e, first_env, num_envs, nullptr, nullptr, (hipStream_t)stream);
+  return RP_OK;
+}
+
+/* the one path behind rp_render_ex and rp_render_layers: views_check, entry_draw */
 static int render_views(rp_handle h, const char* who, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int metres, int32_t width,
                         int32_t height, int32_t first_env, int32_t num_envs, uint8_t* rgb, float* depth, int32_t* segmentation, const float* sub_goal,
                         const float* ghost_arm, void* stream) {
-  RpViews v;
-  int rc = views_check(h, who, cam, cam_rows, near_plane, far_plane, metres, width, height, first_env, num_envs, ghost_arm, &v);
+  RpViewEntry e;
+  int rc = views_check(h, who, cam, cam_rows, near_plane, far_plane, metres, width, height, first_env, num_envs, ghost_arm, &e);
   if (rc != RP_OK) return rc;
+  e.rgb = rgb; e.depth = depth; e.seg = segmentation;
   DevGuard guard(h->cfg.device);
-  rc = rc_reserve(h, num_envs);
+  rc = entry_draw(h, e, first_env, num_envs, sub_goal, ghost_arm, stream);
   if (rc != RP_OK) return rc;
-  h->rc_last_num = num_envs;
-  views_launch(h, v, first_env, rgb, depth, segmentation, sub_goal, ghost_arm, nullptr, nullptr, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return RP_OK;
 }
@@ -1182,89 +1179,67 @@ static const char* layers_complaint(const rp_camera* cam, const float* cam_rows,
   return nullptr;
 }
 
-/* The image observations: every check is made here, once, and the stepping calls only launch (image_pass).  The pose table is reserved for all N envs here, so that no
- * stepping call allocates; where that replaces a smaller table, hipFree waits for the device, and so does this call before it replaces a configuration that calls in
- * flight on other streams were launched with (their kernels hold the old pointers; the caller may free those buffers once this call has returned). */
-int rp_set_image_obs(rp_handle h, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int32_t depth_mode, int32_t width, int32_t height,
-                     uint8_t* rgb, float* depth, int32_t* segmentation, uint8_t* final_rgb, float* final_depth, int32_t* final_segmentation) {
-  if (!h) return RP_ERR_ARG;
-  DevGuard guard(h->cfg.device);
-  if (width == 0 && height == 0) {
-    if (h->io_on) HIPCHK(h, hipDeviceSynchronize());
-    h->io_on = 0; h->io_final = 0;
-    points_drop(h);
-    return RP_OK;
-  }
-  const char* bad = layers_complaint(cam, cam_rows, near_plane, far_plane, depth_mode, rgb, depth, segmentation);
-  if (bad) { snprintf(h->err, 256, "rp_set_image_obs: %s", bad); return RP_ERR_ARG; }
-  RpViews v;
-  int rc = views_check(h, "rp_set_image_obs", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, 0, h->cfg.num_envs, nullptr, &v);
-  if (rc != RP_OK) return rc;
-  if (h->io_on) HIPCHK(h, hipDeviceSynchronize());
-  points_drop(h);      /* rp_set_image_points' clouds go with the configuration they were attached to */
-  rc = rc_reserve(h, h->cfg.num_envs);
-  if (rc != RP_OK) { h->io_on = 0; h->io_final = 0; return rc; }      /* (the table it had may be gone) */
-  h->io = v;
-  h->io_rgb = rgb; h->io_depth = depth; h->io_seg = segmentation;
-  /* a terminal layer without its observation layer is drawn all the same: the final_* pointers stand for themselves */
-  h->io_frgb = final_rgb; h->io_fdepth = final_depth; h->io_fseg = final_segmentation;
-  h->io_final = (final_rgb || final_depth || final_segmentation) ? 1 : 0;
-  h->io_on = 1;
-  return RP_OK;
-}
-
-/* Several views per env.  One view is rp_set_image_obs' configuration and takes its path and its launches; two or more fill k_render_views' two tables here, so that
- * a stepping call only launches (views_pass).  Every view is checked before anything changes: a refusal leaves the configuration in force as it was. */
-int rp_set_image_views(rp_handle h, const rp_image_view* views, int32_t n_views) {
-  if (!h) return RP_ERR_ARG;
-  if (n_views < 0 || n_views > RP_MAX_IMAGE_VIEWS) { snprintf(h->err, 256, "rp_set_image_views: n_views = %d lies outside 0 .. %d", n_views, RP_MAX_IMAGE_VIEWS); return RP_ERR_ARG; }
-  if (n_views == 0) return rp_set_image_obs(h, nullptr, nullptr, 0.f, 0.f, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  if (!views) { snprintf(h->err, 256, "rp_set_image_views: views is NULL with n_views = %d", n_views); return RP_ERR_ARG; }
+/* The image configuration: every check is made here, once, and the stepping calls only launch (image_pass).  `who` is the entry point; with `numbered` a complaint
+ * about view k names it ("<who>: view k: ...").  Every view is checked before anything changes: a refusal leaves the configuration in force as it was.  n = 0
+ * switches it off.  The pose table is reserved for all N envs here, so that no stepping call allocates; where that replaces a smaller table, hipFree waits for the
+ * device, and so does this call before it replaces a configuration that calls in flight on other streams were launched with (their kernels hold the old pointers;
+ * the caller may free those buffers once this call has returned). */
+static int image_config_set(rp_handle h, const char* who, bool numbered, const rp_image_view* views, int n) {
   const int N = h->cfg.num_envs;
-  RpViewTable obs, fin;
-  memset(&obs, 0, sizeof(obs)); memset(&fin, 0, sizeof(fin));
-  int nf = 0; long long tiles = 0, ftiles = 0;
-  int fmap[RC_MAX_VIEWS] = {-1, -1, -1, -1};
-  for (int k = 0; k < n_views; k++) {
+  RpImageConfig c;
+  memset(&c, 0, sizeof(c));
+  for (int k = 0; k < RC_MAX_VIEWS; k++) c.fmap[k] = -1;
+  long long tiles = 0, ftiles = 0;
+  for (int k = 0; k < n; k++) {
     const rp_image_view& w = views[k];
-    char who[48];
-    snprintf(who, sizeof(who), "rp_set_image_views: view %d", k);
+    char name[48];
+    if (numbered) snprintf(name, sizeof(name), "%s: view %d", who, k);
+    else snprintf(name, sizeof(name), "%s", who);
     const char* bad = layers_complaint(w.cam, w.cam_rows, w.near_plane, w.far_plane, w.depth_mode, w.rgb, w.depth, w.segmentation);
-    if (bad) { snprintf(h->err, 256, "%s: %s", who, bad); return RP_ERR_ARG; }
-    RpViews v;
-    int rc = views_check(h, who, w.cam, w.cam_rows, w.near_plane, w.far_plane, w.depth_mode == RP_DEPTH_METRES ? 1 : 0, w.width, w.height, 0, N, nullptr, &v);
-    if (rc != RP_OK) return rc;
+    if (bad) { snprintf(h->err, 256, "%s: %s", name, bad); return RP_ERR_ARG; }
     RpViewEntry e;
-    memset(&e, 0, sizeof(e));
-    e.cam = v.cam; e.cam_rows = v.cam_rows; e.width = v.width; e.height = v.height;
-    e.tiles_x = (v.width + 15) / 16; e.tiles = e.tiles_x * ((v.height + 15) / 16);
-    e.near_plane = v.near_plane; e.far_plane = v.far_plane; e.metres = v.metres;
+    int rc = views_check(h, name, w.cam, w.cam_rows, w.near_plane, w.far_plane, w.depth_mode == RP_DEPTH_METRES ? 1 : 0, w.width, w.height, 0, N, nullptr, &e);
+    if (rc != RP_OK) return rc;
     e.tile0 = (int)tiles; e.rgb = w.rgb; e.depth = w.depth; e.seg = w.segmentation;
-    obs.v[k] = e;
+    c.obs.v[k] = e;
     tiles += e.tiles;
+    /* a terminal layer without its observation layer is drawn all the same: the final_* pointers stand for themselves */
     if (w.final_rgb || w.final_depth || w.final_segmentation) {
       e.tile0 = (int)ftiles; e.rgb = w.final_rgb; e.depth = w.final_depth; e.seg = w.final_segmentation;
-      fmap[k] = nf;
-      fin.v[nf++] = e;
+      c.fmap[k] = c.n_fin;
+      c.fin.v[c.n_fin++] = e;
       ftiles += e.tiles;
     }
   }
-  if ((long long)N * tiles > 0x7fffffffLL) { snprintf(h->err, 256, "rp_set_image_views: %lld tiles of %d views exceed one launch", (long long)N * tiles, n_views); return RP_ERR_ARG; }
-  if (n_views == 1) {
-    const rp_image_view& w = views[0];
-    return rp_set_image_obs(h, w.cam, w.cam_rows, w.near_plane, w.far_plane, w.depth_mode, w.width, w.height, w.rgb, w.depth, w.segmentation, w.final_rgb, w.final_depth,
-                            w.final_segmentation);
-  }
+  if ((long long)N * tiles > 0x7fffffffLL) { snprintf(h->err, 256, "%s: %lld tiles of %d views exceed one launch", who, (long long)N * tiles, n); return RP_ERR_ARG; }
   DevGuard guard(h->cfg.device);
-  if (h->io_on) HIPCHK(h, hipDeviceSynchronize());
-  points_drop(h);
+  if (h->img.n) HIPCHK(h, hipDeviceSynchronize());
+  h->img.n = 0;      /* (off until the pose table stands: a failed reserve may have freed the one it had) */
+  points_drop(h);    /* rp_set_image_points' clouds go with the configuration they were attached to */
+  if (n == 0) return RP_OK;
   int rc = rc_reserve(h, N);
-  if (rc != RP_OK) { h->io_on = 0; h->io_final = 0; return rc; }      /* (the table it had may be gone) */
-  for (int k = 0; k < RC_MAX_VIEWS; k++) h->iv_fmap[k] = fmap[k];
-  h->iv_obs = obs; h->iv_fin = fin; h->iv_n = n_views; h->iv_fn = nf; h->iv_tiles = (int)tiles; h->iv_ftiles = (int)ftiles;
-  h->io_final = nf > 0 ? 1 : 0;
-  h->io_on = 2;
+  if (rc != RP_OK) return rc;
+  c.n = n; c.tiles = (int)tiles; c.ftiles = (int)ftiles;
+  h->img = c;
   return RP_OK;
+}
+
+int rp_set_image_obs(rp_handle h, const rp_camera* cam, const float* cam_rows, float near_plane, float far_plane, int32_t depth_mode, int32_t width, int32_t height,
+                     uint8_t* rgb, float* depth, int32_t* segmentation, uint8_t* final_rgb, float* final_depth, int32_t* final_segmentation) {
+  if (!h) return RP_ERR_ARG;
+  rp_image_view w;
+  memset(&w, 0, sizeof(w));
+  w.cam = cam; w.cam_rows = cam_rows; w.near_plane = near_plane; w.far_plane = far_plane; w.depth_mode = depth_mode; w.width = width; w.height = height;
+  w.rgb = rgb; w.depth = depth; w.segmentation = segmentation; w.final_rgb = final_rgb; w.final_depth = final_depth; w.final_segmentation = final_segmentation;
+  return image_config_set(h, "rp_set_image_obs", false, &w, width == 0 && height == 0 ? 0 : 1);
+}
+
+/* Several views per env: the same configuration with up to RP_MAX_IMAGE_VIEWS entries */
+int rp_set_image_views(rp_handle h, const rp_image_view* views, int32_t n_views) {
+  if (!h) return RP_ERR_ARG;
+  if (n_views < 0 || n_views > RP_MAX_IMAGE_VIEWS) { snprintf(h->err, 256, "rp_set_image_views: n_views = %d lies outside 0 .. %d", n_views, RP_MAX_IMAGE_VIEWS); return RP_ERR_ARG; }
+  if (n_views > 0 && !views) { snprintf(h->err, 256, "rp_set_image_views: views is NULL with n_views = %d", n_views); return RP_ERR_ARG; }
+  return image_config_set(h, "rp_set_image_views", true, views, n_views);
 }
 
 /* test seam and benchmark control: on = 0 draws the views of a pass as one k_render_layers launch each (the default is on: one k_render_views launch) */
@@ -1310,13 +1285,13 @@ int rp_render_states(rp_handle h, const rp_state_rows* src, int32_t m, const rp_
   else if (goal_mode != RP_GOAL_GHOST && goal_mode != RP_GOAL_SOLID) bad = "unknown goal_mode";
   if (!bad) bad = layers_complaint(cam, cam_rows, near_plane, far_plane, depth_mode, rgb, depth, segmentation);
   if (bad) { snprintf(h->err, 256, "rp_render_states: %s", bad); return RP_ERR_ARG; }
-  RpViews v;
-  int rc = views_check(h, "rp_render_states", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, 0, 1, nullptr, &v);
+  RpViewEntry e;
+  int rc = views_check(h, "rp_render_states", cam, cam_rows, near_plane, far_plane, depth_mode == RP_DEPTH_METRES ? 1 : 0, width, height, 0, 1, nullptr, &e);
   if (rc != RP_OK) return rc;
   const float* rows = src->rows ? (const float*)src->rows : h->state;
   const size_t row_floats = src->rows ? src->row_stride / sizeof(float) : (size_t)RP_REC_FLOATS;
   const int n_rows = src->rows ? src->n_rows : N;
-  const long long tiles = (long long)((width + 15) / 16) * ((height + 15) / 16);       /* <= 65536: a chunk never falls below 32767 images */
+  const long long tiles = e.tiles;       /* <= 65536: a chunk never falls below 32767 images */
   long long cap = h->rs_chunk > 0 ? h->rs_chunk : (N > 4096 ? N : 4096);
   if (cap > m) cap = m;
   if (cap * tiles > 0x7fffffffLL) cap = 0x7fffffffLL / tiles;
@@ -1333,8 +1308,8 @@ int rp_render_states(rp_handle h, const rp_state_rows* src, int32_t m, const rp_
     const float* g = goal ? goal + (size_t)base * n_ag : nullptr;
     hipLaunchKernelGGL(goal_mode == RP_GOAL_SOLID ? k_collider_poses_rows<true> : k_collider_poses_rows<false>, dim3(num), dim3(64), 0, s, h->dev_model, rows, row_floats,
                        n_rows, idx, (int)base, num, h->rc_tab, h->rc_cnt, g, h->rc_ee, (const float*)h->vis, ve, N);
-    hipLaunchKernelGGL(k_render_states, dim3((unsigned)(num * tiles)), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, num, v.cam,
-                       cam_rows ? cam_rows + 11 * (size_t)base : nullptr, h->rc_ee, width, height, cull, near_plane, far_plane, v.metres,
+    hipLaunchKernelGGL(k_render_states, dim3((unsigned)(num * tiles)), dim3(256), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, num, e.cam,
+                       cam_rows ? cam_rows + 11 * (size_t)base : nullptr, h->rc_ee, width, height, cull, near_plane, far_plane, e.metres,
                        rgb ? rgb + 3 * npix * (size_t)base : nullptr, depth ? depth + npix * (size_t)base : nullptr,
                        segmentation ? segmentation + npix * (size_t)base : nullptr, (const float*)h->vis, ve, N, idx, (int)base, n_rows);
   }
@@ -1349,13 +1324,12 @@ int rp_debug_render_states_chunk(rp_handle h, int32_t slots) {
   return RP_OK;
 }
 
-/* one table entry: the view's camera and size, the layers to read, the outputs, the spec */
-static RpPointsEntry points_entry(const RpCamera& cam, const float* cam_rows, int width, int height, const uint8_t* rgb, const float* depth, const int32_t* seg,
-                                  const rp_points_spec* spec, float* xyz, int32_t* point_seg, uint8_t* point_rgb, int32_t* count) {
+/* one table entry: the camera, the size and the layers of view entry v (the layers to read), the spec, the outputs */
+static RpPointsEntry points_entry(const RpViewEntry& v, const rp_points_spec* spec, float* xyz, int32_t* point_seg, uint8_t* point_rgb, int32_t* count) {
   RpPointsEntry e;
   memset(&e, 0, sizeof(e));
-  e.cam = cam; e.cam_rows = cam_rows; e.width = width; e.height = height;
-  e.depth = depth; e.seg = seg; e.rgb = point_rgb ? rgb : nullptr;
+  e.cam = v.cam; e.cam_rows = v.cam_rows; e.width = v.width; e.height = v.height;
+  e.depth = v.depth; e.seg = v.seg; e.rgb = point_rgb ? v.rgb : nullptr;
   e.xyz = xyz; e.pseg = point_seg; e.prgb = point_rgb; e.count = count;
   e.max_points = spec->max_points; e.frame = spec->frame; e.max_depth = spec->max_depth; e.drop = spec->drop;
   return e;
@@ -1373,17 +1347,16 @@ int rp_render_points(rp_handle h, const rp_camera* cam, const float* cam_rows, i
   if (!bad && point_rgb && !rgb) bad = "point_rgb needs the rgb layer buffer";
   if (!bad) bad = layers_complaint(cam, cam_rows, 0.01f, 10.f, RP_DEPTH_METRES, rgb, depth, segmentation);
   if (bad) { snprintf(h->err, 256, "rp_render_points: %s", bad); return RP_ERR_ARG; }
-  RpViews v;
-  int rc = views_check(h, "rp_render_points", cam, cam_rows, 0.01f, 10.f, 1, width, height, first_env, num_envs, nullptr, &v);
+  RpViewEntry e;
+  int rc = views_check(h, "rp_render_points", cam, cam_rows, 0.01f, 10.f, 1, width, height, first_env, num_envs, nullptr, &e);
   if (rc != RP_OK) return rc;
+  e.rgb = rgb; e.depth = depth; e.seg = segmentation;
   DevGuard guard(h->cfg.device);
-  rc = rc_reserve(h, num_envs);
+  rc = entry_draw(h, e, first_env, num_envs, nullptr, nullptr, stream);
   if (rc != RP_OK) return rc;
-  h->rc_last_num = num_envs;
-  views_launch(h, v, first_env, rgb, depth, segmentation, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
   RpPointsTable t;
   memset(&t, 0, sizeof(t));
-  t.v[0] = points_entry(v.cam, v.cam_rows, width, height, rgb, depth, segmentation, spec, xyz, point_seg, point_rgb, count);
+  t.v[0] = points_entry(e, spec, xyz, point_seg, point_rgb, count);
   points_launch(h, t, 1, first_env, num_envs, nullptr, nullptr, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return RP_OK;
@@ -1394,41 +1367,35 @@ int rp_render_points(rp_handle h, const rp_camera* cam, const float* cam_rows, i
 int rp_set_image_points(rp_handle h, int32_t view, const rp_points_spec* spec, float* xyz, int32_t* point_seg, uint8_t* point_rgb, int32_t* count, float* final_xyz,
                         int32_t* final_point_seg, uint8_t* final_point_rgb, int32_t* final_count) {
   if (!h) return RP_ERR_ARG;
-  if (!h->io_on) { snprintf(h->err, 256, "rp_set_image_points: no image configuration is in force (rp_set_image_obs or rp_set_image_views first)"); return RP_ERR_ARG; }
-  const int nv = h->io_on == 2 ? h->iv_n : 1;
-  if (view < 0 || view >= nv) { snprintf(h->err, 256, "rp_set_image_points: view %d lies outside 0 .. %d", view, nv - 1); return RP_ERR_ARG; }
+  RpImageConfig& c = h->img;
+  if (!c.n) { snprintf(h->err, 256, "rp_set_image_points: no image configuration is in force (rp_set_image_obs or rp_set_image_views first)"); return RP_ERR_ARG; }
+  if (view < 0 || view >= c.n) { snprintf(h->err, 256, "rp_set_image_points: view %d lies outside 0 .. %d", view, c.n - 1); return RP_ERR_ARG; }
   DevGuard guard(h->cfg.device);
   if (!spec) {      /* detach: calls in flight may still write the old outputs */
-    if (h->pc_has[view]) { HIPCHK(h, hipDeviceSynchronize()); h->pc_has[view] = 0; h->pc_n--; }
+    if (c.pc_has[view]) { HIPCHK(h, hipDeviceSynchronize()); c.pc_has[view] = 0; c.pc_n--; }
     return RP_OK;
   }
-  /* the view's layers, observation and terminal, and its camera */
-  RpCamera cam; const float* cam_rows; int width, height, metres;
-  const uint8_t *rgb, *frgb = nullptr; const float *depth, *fdepth = nullptr; const int32_t *seg, *fseg = nullptr;
-  if (h->io_on == 2) {
-    const RpViewEntry& e = h->iv_obs.v[view];
-    cam = e.cam; cam_rows = e.cam_rows; width = e.width; height = e.height; metres = e.metres; rgb = e.rgb; depth = e.depth; seg = e.seg;
-    if (h->iv_fmap[view] >= 0) { const RpViewEntry& f = h->iv_fin.v[h->iv_fmap[view]]; frgb = f.rgb; fdepth = f.depth; fseg = f.seg; }
-  } else {
-    cam = h->io.cam; cam_rows = h->io.cam_rows; width = h->io.width; height = h->io.height; metres = h->io.metres;
-    rgb = h->io_rgb; depth = h->io_depth; seg = h->io_seg; frgb = h->io_frgb; fdepth = h->io_fdepth; fseg = h->io_fseg;
-  }
+  /* the view's entries, observation and terminal (without one: no terminal layers) */
+  const RpViewEntry& e = c.obs.v[view];
+  RpViewEntry f;
+  memset(&f, 0, sizeof(f));
+  if (c.fmap[view] >= 0) f = c.fin.v[c.fmap[view]];
   const bool fin = final_xyz || final_point_seg || final_point_rgb || final_count;
   const char* bad = spec_complaint(spec);
-  if (!bad && (!depth || !metres)) bad = "the view has no depth layer in RP_DEPTH_METRES";
-  if (!bad && !seg) bad = "the view has no segmentation layer";
+  if (!bad && (!e.depth || !e.metres)) bad = "the view has no depth layer in RP_DEPTH_METRES";
+  if (!bad && !e.seg) bad = "the view has no segmentation layer";
   if (!bad && !xyz && !count) bad = "no output (xyz and count are both NULL)";
-  if (!bad && point_rgb && !rgb) bad = "point_rgb is given but the view has no rgb layer";
-  if (!bad && fin && (!fdepth || !fseg)) bad = "a final_* output is given but the view has no final depth and segmentation layers";
-  if (!bad && final_point_rgb && !frgb) bad = "final_point_rgb is given but the view has no final rgb layer";
+  if (!bad && point_rgb && !e.rgb) bad = "point_rgb is given but the view has no rgb layer";
+  if (!bad && fin && (!f.depth || !f.seg)) bad = "a final_* output is given but the view has no final depth and segmentation layers";
+  if (!bad && final_point_rgb && !f.rgb) bad = "final_point_rgb is given but the view has no final rgb layer";
   if (bad) { snprintf(h->err, 256, "rp_set_image_points: view %d: %s", view, bad); return RP_ERR_ARG; }
-  if (h->pc_has[view]) HIPCHK(h, hipDeviceSynchronize());      /* replaced: as above */
-  else h->pc_n++;
-  h->pc_obs[view] = points_entry(cam, cam_rows, width, height, rgb, depth, seg, spec, xyz, point_seg, point_rgb, count);
-  h->pc_has[view] = 1;
+  if (c.pc_has[view]) HIPCHK(h, hipDeviceSynchronize());      /* replaced: as above */
+  else c.pc_n++;
+  c.pc_obs[view] = points_entry(e, spec, xyz, point_seg, point_rgb, count);
+  c.pc_has[view] = 1;
   if (fin) {
-    h->pc_fin[view] = points_entry(cam, cam_rows, width, height, frgb, fdepth, fseg, spec, final_xyz, final_point_seg, final_point_rgb, final_count);
-    h->pc_has[view] |= 2;
+    c.pc_fin[view] = points_entry(f, spec, final_xyz, final_point_seg, final_point_rgb, final_count);
+    c.pc_has[view] |= 2;
   }
   return RP_OK;
 }
@@ -1444,8 +1411,7 @@ int rp_ray_test(rp_handle h, const float* from, const float* to, int32_t k, floa
   int rc = rc_reserve(h, N);
   if (rc != RP_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_collider_poses<false>, dim3(N), dim3(64), 0, s, h->dev_model, h->state, 0, N, h->rc_tab, h->rc_cnt, (const float*)nullptr, (float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, (const int*)nullptr, (const unsigned char*)nullptr);      /* (no colour in a ray test's answer) */
+  poses_launch(h, 0, N, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);      /* (no EE poses, no colour in a ray test's answer) */
   hipLaunchKernelGGL(k_ray_test, dim3(N), dim3(64), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, N, k, from, to, hit_fraction, collider, link, hit_position, hit_normal);
   HIPCHK(h, hipGetLastError());
   return RP_OK;

@@ -77,6 +77,14 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _cam(camera):
+    return C.byref(camera) if camera is not None else None
+
+
+def _depth_mode(depth):
+    return _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER
+
+
 @_per_model
 def dynamics_names(model):
     """{'friction': names of the collision objects, 'mass': names of the free bodies} of a baked model ('U', 'R', 'P', 'Q', 'V', 'W'), in the column
@@ -869,7 +877,7 @@ class VecPlayEnv:
         lo, n, sub_goal, ghost_arm = self._render_args(envs, sub_goal, ghost_arm)
         img = out if out is not None else torch.empty((n, int(height), int(width), 3), dtype=torch.uint8, device=self.device)
         assert img.shape == (n, int(height), int(width), 3) and img.dtype == torch.uint8 and img.is_contiguous()
-        head = (C.byref(camera) if camera is not None else None, int(width), int(height), lo, n, _ptr(img), _ptr(sub_goal))
+        head = (_cam(camera), int(width), int(height), lo, n, _ptr(img), _ptr(sub_goal))
         if ghost_arm is not None:
             self._call('rp_render_ex', *head, _ptr(ghost_arm), self._stream())
         else:
@@ -933,9 +941,8 @@ class VecPlayEnv:
                 t = torch.empty(shape, dtype=dtype, device=self.device)
             assert t.shape == shape and t.dtype == dtype and t.is_contiguous() and t.is_cuda, (k, t.shape, t.dtype)
             res[k] = t
-        self._call('rp_render_layers', C.byref(camera) if camera is not None else None, _ptr(cameras), float(near), float(far),
-                   _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, lo, n, _ptr(res.get('rgb')), _ptr(res.get('depth')),
-                   _ptr(res.get('segmentation')), _ptr(sub_goal), _ptr(ghost_arm), self._stream())
+        self._call('rp_render_layers', _cam(camera), _ptr(cameras), float(near), float(far), _depth_mode(depth), width, height, lo, n, _ptr(res.get('rgb')),
+                   _ptr(res.get('depth')), _ptr(res.get('segmentation')), _ptr(sub_goal), _ptr(ghost_arm), self._stream())
         return res
 
     POINTS_KEYS = ('n', 'frame', 'max_depth', 'drop', 'colour')
@@ -1005,7 +1012,7 @@ class VecPlayEnv:
         layers, shapes, cameras = self._layer_args('render_points', n, width, height, layers, 'metres', camera, cameras, 0.01, 10.0)
         lay = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
         pts = self._points_tensors(n, spec.max_points, colour)
-        self._call('rp_render_points', C.byref(camera) if camera is not None else None, _ptr(cameras), width, height, lo, n, C.byref(spec), _ptr(lay.get('rgb')),
+        self._call('rp_render_points', _cam(camera), _ptr(cameras), width, height, lo, n, C.byref(spec), _ptr(lay.get('rgb')),
                    _ptr(lay['depth']), _ptr(lay['segmentation']), *self._points_ptrs(pts), self._stream())
         return {**pts, 'layers': lay}
 
@@ -1065,9 +1072,8 @@ class VecPlayEnv:
         index = index.contiguous() if index is not None else None
         visuals = visuals.contiguous() if visuals is not None else None
         src = _lib.RpStateRows(_ptr(states), 4 * states.stride(0) if states is not None else 0, rows, _ptr(index), _ptr(visuals))
-        self._call('rp_render_states', C.byref(src), m, C.byref(camera) if camera is not None else None, _ptr(cameras), float(near), float(far),
-                   _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, _ptr(res.get('rgb')), _ptr(res.get('depth')),
-                   _ptr(res.get('segmentation')), _ptr(goal), _lib.GOAL_SOLID if goal_mode == 'solid' else _lib.GOAL_GHOST, self._stream())
+        self._call('rp_render_states', C.byref(src), m, _cam(camera), _ptr(cameras), float(near), float(far), _depth_mode(depth), width, height, _ptr(res.get('rgb')),
+                   _ptr(res.get('depth')), _ptr(res.get('segmentation')), _ptr(goal), _lib.GOAL_SOLID if goal_mode == 'solid' else _lib.GOAL_GHOST, self._stream())
         return res
 
     def goal_images(self, goal, width, height, camera=None, cameras=None, layers=('rgb', 'depth', 'segmentation'), depth='buffer', near=0.01, far=10.0, out=None):
@@ -1080,6 +1086,22 @@ class VecPlayEnv:
     def _image_keys(t):
         """the observation's image keys of a set_image_obs tensor dict: 'img' (the rgb tensor, None unless asked for), 'depth' and 'segmentation' where asked for"""
         return {'img': t.get('rgb'), **{k: t[k] for k in ('depth', 'segmentation') if k in t}}
+
+    def _image_view(self, who, width, height, layers, camera, cameras, depth, near, far, terminal=True, points=None):
+        """set_image_obs' and a view of set_image_views' host-side checks (ValueError; `who` names the call and the view) and tensors: (width, height, cameras, the
+        zeroed observation tensors {layer: tensor}, the terminal ones - None without autoreset or with terminal=False)"""
+        width, height = int(width), int(height)
+        if cameras is not None and isinstance(cameras, torch.Tensor) and not cameras.is_contiguous():
+            raise ValueError('%s: cameras must be contiguous (it is read in place at every draw)' % who)
+        layers, shapes, cameras = self._layer_args(who, self.num_envs, width, height, layers, depth, camera, cameras, near, far)
+        if not (0 < width <= 4096 and 0 < height <= 4096):
+            raise ValueError('%s: width and height lie in 1 .. 4096, not %d x %d' % (who, width, height))
+        if points is not None:
+            self._points_of_view(who, points, layers, depth)      # (checked before anything changes; attached by the caller)
+
+        def alloc():
+            return {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
+        return width, height, cameras, alloc(), alloc() if self.autoreset and terminal else None
 
     def set_image_obs(self, width=84, height=84, layers=('rgb',), camera=None, cameras=None, depth='buffer', near=0.01, far=10.0):
         """Camera images as part of the observation (rp_set_image_obs): from now on step, reset, reset(o=...) and calc_state draw the chosen layers of every env whose
@@ -1101,20 +1123,9 @@ class VecPlayEnv:
             self._call('rp_set_image_obs', None, None, 0.0, 0.0, 0, 0, 0, None, None, None, None, None, None)
             self._no_images()
             return
-        N = self.num_envs
-        width, height = int(width), int(height)
-        if cameras is not None and isinstance(cameras, torch.Tensor) and not cameras.is_contiguous():
-            raise ValueError('set_image_obs: cameras must be contiguous (it is read in place at every draw)')
-        layers, shapes, cameras = self._layer_args('set_image_obs', N, width, height, layers, depth, camera, cameras, near, far)
-        if not (0 < width <= 4096 and 0 < height <= 4096):
-            raise ValueError('set_image_obs: width and height lie in 1 .. 4096, not %d x %d' % (width, height))
-
-        def alloc():
-            return {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
-        obs, final = alloc(), alloc() if self.autoreset else None
+        width, height, cameras, obs, final = self._image_view('set_image_obs', width, height, layers, camera, cameras, depth, near, far)
         ptrs = [_ptr(t.get(k)) for t in (obs, final or {}) for k in ('rgb', 'depth', 'segmentation')]
-        self._call('rp_set_image_obs', C.byref(camera) if camera is not None else None, _ptr(cameras), float(near), float(far),
-                   _lib.DEPTH_METRES if depth == 'metres' else _lib.DEPTH_BUFFER, width, height, *ptrs)
+        self._call('rp_set_image_obs', _cam(camera), _ptr(cameras), float(near), float(far), _depth_mode(depth), width, height, *ptrs)
         self._no_images()      # (the handle has one image configuration: this call replaced set_image_views' too)
         self.image_obs, self.image_final, self.image_cameras, self._image_depth = obs, final, cameras, depth
         self._kept['rp_set_image_obs'] = (obs, final, cameras)      # (kept until the next set: the library writes and reads them at every draw)
@@ -1193,28 +1204,18 @@ class VecPlayEnv:
             return
         if not hasattr(views, 'items') or not 1 <= len(views) <= _lib.MAX_IMAGE_VIEWS:
             raise ValueError('set_image_views: views is a mapping of 1 to %d names to dicts of set_image_obs\' arguments' % _lib.MAX_IMAGE_VIEWS)
-        N = self.num_envs
         arr = (_lib.RpImageView * len(views))()
-        obs, final, cams, keep = {}, {}, {}, []
+        obs, final, cams, depths, keep = {}, {}, {}, {}, []
         defaults = dict(width=84, height=84, layers=('rgb',), camera=None, cameras=None, depth='buffer', near=0.01, far=10.0, terminal=True, points=None)
-        depths = {}
         for i, (name, kw) in enumerate(views.items()):
             who = 'set_image_views: view %r' % (name,)
             if not hasattr(kw, 'keys') or set(kw) - set(defaults):
                 raise ValueError('%s: a dict with keys among %s, not %r' % (who, sorted(defaults), kw))
             a = {**defaults, **kw}
-            width, height, cameras = int(a['width']), int(a['height']), a['cameras']
-            if cameras is not None and isinstance(cameras, torch.Tensor) and not cameras.is_contiguous():
-                raise ValueError('%s: cameras must be contiguous (it is read in place at every draw)' % who)
-            layers, shapes, cameras = self._layer_args(who, N, width, height, a['layers'], a['depth'], a['camera'], cameras, a['near'], a['far'])
-            if not (0 < width <= 4096 and 0 < height <= 4096):
-                raise ValueError('%s: width and height lie in 1 .. 4096, not %d x %d' % (who, width, height))
-            if a['points'] is not None:
-                self._points_of_view(who, a['points'], layers, a['depth'])      # (checked before anything changes; attached below)
+            width, height, cameras, obs[name], fin = self._image_view(who, **a)
             depths[name] = a['depth']
-            obs[name] = {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
-            if self.autoreset and a['terminal']:
-                final[name] = {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in layers}
+            if fin is not None:
+                final[name] = fin
             if cameras is not None:
                 cams[name] = cameras
             v = arr[i]
@@ -1222,12 +1223,10 @@ class VecPlayEnv:
                 keep.append(a['camera'])
                 v.cam = C.pointer(a['camera'])
             v.cam_rows = cameras.data_ptr() if cameras is not None else None
-            v.near_plane, v.far_plane, v.depth_mode = float(a['near']), float(a['far']), _lib.DEPTH_METRES if a['depth'] == 'metres' else _lib.DEPTH_BUFFER
-            v.width, v.height = width, height
-            for k in layers:
-                setattr(v, k, obs[name][k].data_ptr())
-                if name in final:
-                    setattr(v, 'final_' + k, final[name][k].data_ptr())
+            v.near_plane, v.far_plane, v.depth_mode, v.width, v.height = float(a['near']), float(a['far']), _depth_mode(a['depth']), width, height
+            for prefix, tensors in (('', obs[name]), ('final_', fin or {})):
+                for k, t in tensors.items():
+                    setattr(v, prefix + k, t.data_ptr())
         self._call('rp_set_image_views', arr, len(views))
         self._no_images()
         self.image_views, self.image_views_final, self.image_view_cameras, self._image_depth = obs, (final if self.autoreset else None), cams, depths

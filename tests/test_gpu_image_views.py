@@ -330,6 +330,138 @@ def test_one_configuration_per_handle():
     X.close()
 
 
+def staggered_autoreset(envs, steps, seed, limit=3):
+    """reset, counters e % limit, and the (actions, end_masks) of `steps` steps for handles made with autoreset=True and max_episode_steps=limit: the time limit ends
+    some envs in the first steps, end_mask all of them in step 2 and - the counters being level then - nothing ends in step 3"""
+    n, dev = envs[0].num_envs, envs[0].device
+    for env in envs:
+        env.reset()
+        env.episode_steps = torch.arange(n, device=dev, dtype=torch.int32) % limit
+    masks = end_masks(n, steps, seed + 1, dev, p=0.2)
+    if steps > 3:
+        masks[2] = torch.ones(n, device=dev, dtype=torch.uint8)
+        masks[3] = torch.zeros(n, device=dev, dtype=torch.uint8)
+    return actions(envs[0], steps, seed), masks
+
+
+def flat(d, prefix=''):
+    """{'layer' or 'points/key': tensor} of a view's tensor dict"""
+    out = {}
+    for k, t in d.items():
+        out.update(flat(t, k + '/') if isinstance(t, dict) else {prefix + k: t})
+    return out
+
+
+def fill_sentinel_deep(d):
+    fill_sentinel({k: t for k, t in d.items() if not isinstance(t, dict)})
+    for t in d.values():
+        if isinstance(t, dict):
+            fill_sentinel(t)
+
+
+def test_one_view_is_a_table_of_one():
+    """One view with a cloud, configured three ways: A by set_image_obs + set_image_points, B by set_image_views with the merge switch on, C the same with it off.
+    Same seed, actions and end_masks over 6 autoreset steps (time limit 3, staggered; step 2 ends every env, step 3 none): every observation layer and cloud, every
+    terminal layer and cloud, done and reset_row are equal across the three, byte for byte; the terminal rows of envs that did not end keep the sentinel; env 3's
+    observation rows equal A's render_layers(envs=(3, 4))."""
+    n, steps, seed = 5, 6, 21
+    envs = [make(U, n, seed, autoreset=True, max_episode_steps=3) for _ in range(3)]
+    A, B, Cc = envs
+    cloud = dict(n=64, colour=True)
+    spec = dict(width=33, height=50, layers=ALL, depth='metres', cameras=per_env_cameras(A))
+    A.set_image_obs(**spec)
+    A.set_image_points(**cloud)
+    for env, on in ((B, 1), (Cc, 0)):
+        set_merge(env, on)
+        env.set_image_views({'img': dict(points=cloud, **{**spec, 'cameras': per_env_cameras(env)})})
+    acts, masks = staggered_autoreset(envs, steps, seed)
+
+    def tensors(env, obs, info):
+        """(observation, terminal) tensors by 'layer' / 'points/key', named alike for the two ways to configure the view"""
+        term = info['terminal_observation']
+        if env is A:
+            return tuple(flat({**{k: o['img' if k == 'rgb' else k] for k in ALL}, 'points': o['points']}) for o in (obs, term))
+        return flat(obs['views']['img']), flat(term['views']['img'])
+
+    names = set(ALL) | {'points/' + k for k in ('xyz', 'segmentation', 'count', 'rgb')}
+    ends = []
+    for t in range(steps):
+        fill_sentinel(A.image_final)
+        fill_sentinel(A.image_points_final)
+        for env in (B, Cc):
+            fill_sentinel_deep(env.image_views_final['img'])
+        got = []
+        for env in envs:
+            obs, _, done, info = env.step(acts[t], end_mask=masks[t])
+            got.append(tensors(env, obs, info) + (done, info['reset_row']))
+        torch.cuda.synchronize()
+        (oa, ta, da, ra) = got[0]
+        assert set(oa) == set(ta) == names
+        for which, (o, term, done, row) in zip('BC', got[1:]):
+            assert set(o) == set(term) == names, which
+            assert torch.equal(done, da) and torch.equal(row, ra), (t, which)
+            for k in names:
+                assert same_bytes(o[k], oa[k]), (t, which, 'obs', k)
+                assert same_bytes(term[k], ta[k]), (t, which, 'terminal', k)
+        ended = [bool(x) for x in da.cpu()]
+        ends.append(sum(ended))
+        for which, (_, term, _, _) in zip('ABC', got):
+            for k in names:
+                for i in range(n):
+                    if not ended[i]:
+                        assert is_sentinel(k.split('/')[-1], term[k][i]), (t, which, k, i)
+        for i in range(n):
+            if ended[i]:
+                assert not is_sentinel('rgb', ta['rgb'][i]), (t, i)
+        e = 3
+        want = A.render_layers(layers=ALL, envs=(e, e + 1), **render_kw(spec, e))
+        for k in ALL:
+            assert same_bytes(oa[k][e:e + 1], want[k]), (t, k)
+    assert ends[2] == n and ends[3] == 0 and 0 < ends[0] < n, ends
+    for env in envs:
+        env.close()
+
+
+def test_a_two_view_configuration_with_one_terminal_view():
+    """two views of which the first has no terminal frames: the terminal pass of this TWO-view configuration has one entry.  A handle with the merge switch on and one
+    with it off, same seed, 4 autoreset steps (time limit 3, staggered): the observation tensors of both views and the terminal tensors of the one terminal view are
+    equal byte for byte, the terminal rows of envs that did not end keep the sentinel, and image_views_final has that view alone"""
+    n, steps, seed = 5, 4, 21
+    envs = [make(U, n, seed, autoreset=True, max_episode_steps=3) for _ in range(2)]
+    for env, on in zip(envs, (1, 0)):
+        set_merge(env, on)
+        specs = two_views(env)
+        specs['tile']['terminal'] = False
+        env.set_image_views(specs)
+        assert list(env.image_views_final) == ['wrist'] and set(env.image_views_final['wrist']) == {'rgb', 'depth'}
+    M, S = envs
+    acts, masks = staggered_autoreset(envs, steps, seed)
+    ends = []
+    for t in range(steps):
+        for env in envs:
+            fill_sentinel(env.image_views_final['wrist'])
+        om, _, dm, im = M.step(acts[t], end_mask=masks[t])
+        os_, _, ds, is_ = S.step(acts[t], end_mask=masks[t])
+        torch.cuda.synchronize()
+        assert torch.equal(dm, ds), t
+        assert list(om['views']) == list(os_['views']) == ['tile', 'wrist']
+        for name in ('tile', 'wrist'):
+            assert set(om['views'][name]) == set(os_['views'][name]) == set(specs[name]['layers'])
+            for k in specs[name]['layers']:
+                assert same_bytes(om['views'][name][k], os_['views'][name][k]), (t, name, k)
+        tm, ts = im['terminal_observation']['views'], is_['terminal_observation']['views']
+        assert list(tm) == list(ts) == ['wrist']
+        ended = [bool(x) for x in dm.cpu()]
+        ends.append(sum(ended))
+        for k in ('rgb', 'depth'):
+            assert same_bytes(tm['wrist'][k], ts['wrist'][k]), (t, k)
+            for i in range(n):
+                assert is_sentinel(k, tm['wrist'][k][i]) == (not ended[i]), (t, k, i)
+    assert ends[2] == n and ends[3] == 0 and 0 < ends[0] < n, ends
+    for env in envs:
+        env.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 # 7: refusals
 
