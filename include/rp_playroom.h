@@ -419,6 +419,46 @@ int rp_render_states(rp_handle h, const rp_state_rows* src, int32_t m,
                      uint8_t* rgb, float* depth, int32_t* segmentation,       /* [m, h, w, 3] / [m, h, w] / [m, h, w]; each may be NULL, not all three */
                      const float* goal /* device [m, dims.achieved_goal] or NULL */, int32_t goal_mode, void* stream);
 
+/* ---- closest points between colliders, live or from stored state rows ------------------------------------------------------------------------------
+ * bullet_client.getClosestPoints for k collider pairs of each of m rows: how far apart two shapes are and where their nearest points lie.  The rows are
+ * rp_render_states' - src NULL or src->rows NULL: the handle's live envs (m <= N unless row_index is given); else rows of a caller's device buffer in rp_get_state's
+ * layout, gathered by src->row_index; src->vis_env is ignored.
+ * THE SHAPES are the ones rp_ray_test and the camera meet, WITHOUT MARGINS: a box collider is its exact box, a sphere is centre and radius, an arm or static robot
+ * link with a collision hull is the convex hull of its baked vertices, a robot link without one its box.  Any two colliders of one row may be asked, link against link
+ * included (which the contact model treats as boxes).  Collider numbers are rp_ray_test's (0 .. n_col - 1, rp_get_collider_dims).
+ * pairs: DEVICE int32 [k, 3] = collider a, collider b, group; read by the kernel alone, never on the host.
+ * THE RULE: GJK's distance phase on the two support functions (box: the sign of the direction per axis; sphere: its centre, the radius taken off the distance and the
+ * witness moved along the normal; hull: the scan of the direction's cell of the support-vertex tables, the lowest vertex number among equals), the simplex in double.
+ * The loop is bounded (48 support queries); a pair that reaches the bound reports the best distance it has - an upper bound - with RP_CP_CAPPED OR-ed into its status.
+ * PER PAIR (each output may be NULL, not all of them): distance [m, k] float32, point_a / point_b [m, k, 3] (world), normal [m, k, 3] FROM B TOWARD A (the
+ * contact convention), status [m, k] int32:
+ *   RP_CP_SEPARATED  distance > 0 and point_a - point_b = normal * distance
+ *   RP_CP_OVERLAP    GJK ended with the origin inside its simplex or within its zero threshold - the shapes overlap or touch: distance is exactly 0, point_a and
+ *                    point_b are both GJK's common point, normal is (0, 0, 0).  PENETRATION DEPTH IS NOT REPORTED (it needs an exact expanding polytope on
+ *                    arbitrary hull pairs); the contact model's depths stay the step's business.
+ *   RP_CP_FAR        only with max_distance > 0: the gap of the two shapes' world AABBs (the box around a hull is its record's box), a lower bound of the distance,
+ *                    exceeds max_distance.  GJK is not run: distance = max_distance, the witnesses and the normal are zero.  max_distance <= 0: no cut.  A pair
+ *                    that is not FAR gets the very bits the call without a cut gives it.
+ *   RP_CP_SKIPPED    collider a or b outside [0, n_col), a == b, or the row's index outside the buffer: status alone is written, the pair's other outputs KEEP
+ *                    WHAT THEY HELD (rp_copy_envs' and rp_render_states' convention for a bad index) - an early exit, not a fault.
+ * PER ROW AND GROUP (optional; n_groups = G > 0): group_min [m, G] float32 and group_pair [m, G] int32 = the smallest distance over the group's pairs that are not
+ * SKIPPED and the index of that pair, the lowest index among equals; a FAR pair counts with max_distance; an empty group gives +inf and -1; a pair whose group
+ * lies outside [0, G) belongs to no group.  Reduced in the same launch, in LDS, no atomics: the result of a scan in pair order, the same bits on every run.
+ * COST: per chunk of min(m, max(N, 4096)) rows (rp_render_states' chunks of pose-table slots) two launches on `stream` - k_collider_poses_rows without a sub-goal,
+ * k_closest_points (one wave per row, a lane per pair) -; no host wait, no host read of device values; the only allocation is the growth of the pose table.  The call
+ * never writes state rows, the contact cache, counters or any table.  It shares the handle's ONE collider-pose table with every call that draws and with rp_ray_test:
+ * do not overlap it with such a call on another stream.
+ * RP_ERR_ARG (nothing is launched; the message names the cause): m < 1; k outside 1 .. 4096; n_groups outside 0 .. 64; group_min or group_pair given with
+ * n_groups == 0; pairs NULL; every output NULL; max_distance not a number; rp_render_states' row-buffer errors (row_stride < 512 or not a multiple of 4, n_rows < 1,
+ * row_index NULL with m > n_rows - m > N for live rows). */
+enum rp_cp_status { RP_CP_SEPARATED = 0, RP_CP_OVERLAP = 1, RP_CP_FAR = 2, RP_CP_SKIPPED = 3, RP_CP_CAPPED = 4 /* bit */ };
+/* the number of colliders: the range of pairs' a and b (the same number rp_get_visuals_dims gives; this one does not speak of visuals) */
+int rp_get_collider_dims(rp_handle h, int32_t* n_col);
+int rp_closest_points(rp_handle h, const rp_state_rows* src /* NULL or rows NULL: the live envs */, int32_t m,
+                      const int32_t* pairs /* DEVICE [k, 3]: collider a, collider b, group */, int32_t k, int32_t n_groups, float max_distance,
+                      float* distance /* [m, k] */, float* point_a /* [m, k, 3] */, float* point_b, float* normal,
+                      int32_t* status /* [m, k] */, float* group_min /* [m, G] */, int32_t* group_pair /* [m, G] */, void* stream);
+
 /* ---- episodes ended on the device (0.5) ---------------------------------------------------------------------------------------------
  * rp_step_autoreset steps every env as rp_step does (whatever rp_set_fused / rp_set_groups chose) and then resets the envs whose episode ended,
  * on the device: nothing is read back, nothing synchronises, the call returns once the work is enqueued on `stream`.  done[e] (int32 [N]) is

@@ -37,7 +37,8 @@ int rp_debug_render_cull(rp_handle h, int32_t on);
  * tools/image_views_rate.py times one against the other. */
 int rp_debug_image_views_merge(rp_handle h, int32_t on);
 /* rp_render_states' chunks: at most `slots` images per chunk (0, the default: the rule of rp_playroom.h, min(m, max(N, 4096))), so that a test crosses chunk
- * boundaries with seven images instead of 4097.  The images are bit-identical whatever the chunk size (tests/test_gpu_render_states.py).  RP_ERR_ARG: slots < 0. */
+ * boundaries with seven images instead of 4097.  The images are bit-identical whatever the chunk size (tests/test_gpu_render_states.py).  rp_closest_points walks
+ * its rows in the same chunks and obeys the same cap (tests/test_gpu_closest_points.py).  RP_ERR_ARG: slots < 0. */
 int rp_debug_render_states_chunk(rp_handle h, int32_t slots);
 /* rounds the most recent rp_reset took */
 int rp_debug_reset_rounds(rp_handle h);

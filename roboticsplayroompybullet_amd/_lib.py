@@ -102,6 +102,9 @@ class RpStateRows(C.Structure):
 # rp_goal_mode (include/rp_playroom.h)
 GOAL_GHOST, GOAL_SOLID = 0, 1
 STATE_RECORD_BYTES = 512     # the state record: what rp_render_states reads of a row
+# rp_cp_status (include/rp_playroom.h): a pair's status of rp_closest_points; CP_CAPPED is a bit OR-ed in
+CP_SEPARATED, CP_OVERLAP, CP_FAR, CP_SKIPPED, CP_CAPPED = 0, 1, 2, 3, 4
+CP_MAX_PAIRS, CP_MAX_GROUPS = 4096, 64
 
 
 class RpTimers(C.Structure):
@@ -117,7 +120,7 @@ EXPORTS = ['rp_create', 'rp_destroy', 'rp_get_dims', 'rp_reset', 'rp_reset_to', 
            'rp_get_dynamics_dims', 'rp_set_dynamics', 'rp_get_dynamics', 'rp_get_wrench_dims', 'rp_set_wrench', 'rp_get_wrench',
            'rp_get_actuation_dims', 'rp_set_actuation', 'rp_get_actuation', 'rp_get_kinematics', 'rp_set_kinematics', 'rp_copy_envs',
            'rp_get_visuals_dims', 'rp_set_visuals', 'rp_get_visuals', 'rp_set_image_obs', 'rp_set_image_views',
-           'rp_render_points', 'rp_set_image_points', 'rp_render_states']
+           'rp_render_points', 'rp_set_image_points', 'rp_render_states', 'rp_get_collider_dims', 'rp_closest_points']
 # include/rp_playroom_debug.h: test / tuning hooks
 DEBUG_EXPORTS = ['rp_set_fused', 'rp_set_groups', 'rp_set_debug_flags', 'rp_debug_substep', 'rp_debug_row_counts', 'rp_debug_reset_rounds', 'rp_debug_ghost_joints',
                  'rp_debug_autoreset_shape', 'rp_debug_action', 'rp_debug_render_cull', 'rp_debug_image_views_merge',
@@ -197,6 +200,8 @@ def load(wide=False):
     lib.rp_render_states.argtypes = [vp, C.POINTER(RpStateRows), C.c_int32, C.POINTER(RpCamera), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp,
                                      vp, C.c_int32, vp]
     lib.rp_ray_test.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
+    lib.rp_get_collider_dims.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.rp_closest_points.argtypes = [vp, C.POINTER(RpStateRows), C.c_int32, vp, C.c_int32, C.c_int32, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rp_debug_substep.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
     lib.rp_set_fused.argtypes = [vp, C.c_int32]
     lib.rp_set_groups.argtypes = [vp, C.c_int32]

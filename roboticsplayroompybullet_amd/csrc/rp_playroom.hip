@@ -15,6 +15,7 @@
 #include "rp_device_model.h"
 #include "rp_kernels.cuh"
 #include "rp_render.cuh"
+#include "rp_closest.cuh"
 
 
 /* a by-value kernel argument (k_render_views' table) and the host's one record of a view: its layout must not move */
@@ -1413,6 +1414,60 @@ int rp_ray_test(rp_handle h, const float* from, const float* to, int32_t k, floa
   hipStream_t s = (hipStream_t)stream;
   poses_launch(h, 0, N, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);      /* (no EE poses, no colour in a ray test's answer) */
   hipLaunchKernelGGL(k_ray_test, dim3(N), dim3(64), 0, s, h->dev_model, h->rc_tab, h->rc_cnt, N, k, from, to, hit_fraction, collider, link, hit_position, hit_normal);
+  HIPCHK(h, hipGetLastError());
+  return RP_OK;
+}
+
+int rp_get_collider_dims(rp_handle h, int32_t* n_col) {
+  if (!h || !n_col) return RP_ERR_ARG;
+  *n_col = h->host_model.n_col;
+  return RP_OK;
+}
+
+/* Closest points between colliders of m rows - the live envs or rows of a caller's buffer: per chunk of rows (rp_render_states' chunks of pose-table slots)
+ * k_collider_poses_rows without a sub-goal and k_closest_points on `stream`, every output moved to the chunk's first row on the host.  Only the pose table is written
+ * (and grown, by rc_reserve, to the chunk size); `pairs` is read by the kernel alone. */
+int rp_closest_points(rp_handle h, const rp_state_rows* src, int32_t m, const int32_t* pairs, int32_t k, int32_t n_groups, float max_distance, float* distance,
+                      float* point_a, float* point_b, float* normal, int32_t* status, float* group_min, int32_t* group_pair, void* stream) {
+  if (!h) return RP_ERR_ARG;
+  const int N = h->cfg.num_envs;
+  const bool stored = src && src->rows;
+  const char* bad = nullptr;
+  if (m < 1) bad = "m < 1";
+  else if (k < 1 || k > RP_CP_MAX_PAIRS) bad = "k lies outside 1 .. 4096";
+  else if (n_groups < 0 || n_groups > RP_CP_MAX_GROUPS) bad = "n_groups lies outside 0 .. 64";
+  else if ((group_min || group_pair) && n_groups == 0) bad = "group_min / group_pair given with n_groups == 0";
+  else if (!pairs) bad = "pairs is NULL";
+  else if (!distance && !point_a && !point_b && !normal && !status && !group_min && !group_pair) bad = "no output (every output is NULL)";
+  else if (max_distance != max_distance) bad = "max_distance is not a number";
+  else if (stored && src->row_stride < RP_REC_FLOATS * sizeof(float)) bad = "row_stride < 512";
+  else if (stored && src->row_stride % 4 != 0) bad = "row_stride is not a multiple of 4";
+  else if (stored && src->n_rows < 1) bad = "n_rows < 1";
+  else if (!(src && src->row_index) && m > (stored ? src->n_rows : N)) bad = stored ? "m exceeds n_rows and row_index is NULL" : "m exceeds the handle's envs and row_index is NULL (live rows)";
+  if (bad) { snprintf(h->err, 256, "rp_closest_points: %s", bad); return RP_ERR_ARG; }
+  const float* rows = stored ? (const float*)src->rows : h->state;
+  const size_t row_floats = stored ? src->row_stride / sizeof(float) : (size_t)RP_REC_FLOATS;
+  const int n_rows = stored ? src->n_rows : N;
+  const int* row_index = src ? src->row_index : nullptr;
+  long long cap = h->rs_chunk > 0 ? h->rs_chunk : (N > 4096 ? N : 4096);
+  if (cap > m) cap = m;
+  DevGuard guard(h->cfg.device);
+  int rc = rc_reserve(h, (int)cap);
+  if (rc != RP_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int G = (group_min || group_pair) ? n_groups : 0;
+  const size_t lds = (size_t)G * 64 * (sizeof(float) + sizeof(int));
+  for (long long base = 0; base < m; base += cap) {
+    const int num = (int)(m - base < cap ? m - base : cap);
+    const int* idx = row_index ? row_index + base : nullptr;
+    const size_t o = (size_t)base * k, og = (size_t)base * n_groups;
+    hipLaunchKernelGGL(k_collider_poses_rows<false>, dim3(num), dim3(64), 0, s, h->dev_model, rows, row_floats, n_rows, idx, (int)base, num, h->rc_tab, h->rc_cnt,
+                       (const float*)nullptr, (float*)nullptr, (const float*)nullptr, (const int*)nullptr, N);
+    hipLaunchKernelGGL(k_closest_points, dim3(num), dim3(64), lds, s, h->dev_model, h->rc_tab, h->rc_cnt, num, idx, (int)base, n_rows, (const int*)pairs, (int)k, G,
+                       max_distance, distance ? distance + o : nullptr, point_a ? point_a + 3 * o : nullptr, point_b ? point_b + 3 * o : nullptr,
+                       normal ? normal + 3 * o : nullptr, status ? (int*)status + o : nullptr, group_min ? group_min + og : nullptr,
+                       group_pair ? (int*)group_pair + og : nullptr);
+  }
   HIPCHK(h, hipGetLastError());
   return RP_OK;
 }

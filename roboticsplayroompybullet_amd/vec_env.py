@@ -193,6 +193,21 @@ def visual_names(model):
     return tuple(objects[c['obj']] for c in _model(model)['col'])
 
 
+@_per_model
+def collider_names(model):
+    """one UNIQUE name per collider of a baked model, in collider order (the numbers closest_points' pairs, ray_test and the segmentation layer use): visual_names'
+    name - the object's, for an arm collider its link's ('link7') - where that names one collider, and name.ordinal ('drawer.0' .. 'drawer.9', in collider order)
+    where visual_names repeats it"""
+    vis = visual_names(model)
+    seen, out = {}, []
+    for nm in vis:
+        k = seen.get(nm, 0)
+        seen[nm] = k + 1
+        out.append(nm if vis.count(nm) == 1 else '%s.%d' % (nm, k))
+    assert len(set(out)) == len(out), out
+    return tuple(out)
+
+
 VISUAL_WIDTHS = {'colour': 3, 'light': 5, 'background': 3}
 LIGHT_DECIMALS = 7      # decimals a host-side light direction is kept to: those of the default direction's literals (csrc/rp_render.cuh VIS_LIGHT_*)
 
@@ -1250,6 +1265,140 @@ class VecPlayEnv:
         self._call('rp_ray_test', _ptr(f), _ptr(t), k, _ptr(out['hit_fraction']), _ptr(out['collider']), _ptr(out['link']), _ptr(out['hit_position']),
                    _ptr(out['hit_normal']), self._stream())
         return out
+
+    @property
+    def collider_names(self):
+        """one unique name per collider, in collider order: the collider numbers of closest_points' pairs and of ray_test's answer (an object with several colliders:
+        'drawer.0' .. 'drawer.9'; an arm collider: its link, 'link7')"""
+        return collider_names(MODEL_OF[self.env_id])
+
+    def _colliders_of(self, who, x):
+        """the collider numbers one argument of collider_pairs names: an index, a name of collider_names, a name of visual_names (every collider of that object), or a
+        sequence of those"""
+        names, objects = self.collider_names, self.visual_names
+        if isinstance(x, (str, int)) and not isinstance(x, bool):
+            x = [x]
+        out = []
+        try:
+            items = list(x)
+        except TypeError:
+            items = [x]
+        for it in items:
+            if isinstance(it, str):
+                hit = [names.index(it)] if it in names else [c for c, o in enumerate(objects) if o == it]
+                if not hit:
+                    raise ValueError('%s: no collider or object is called %r (collider_names: %s)' % (who, it, ', '.join(names)))
+                out += hit
+            elif isinstance(it, int) and not isinstance(it, bool):
+                if not 0 <= it < len(names):
+                    raise ValueError('%s: collider %d lies outside 0 .. %d' % (who, it, len(names) - 1))
+                out.append(it)
+            else:
+                raise ValueError('%s: a collider is a name or an index, not %r' % (who, it))
+        return out
+
+    def collider_pairs(self, a, b, group=0):
+        """the pair list of closest_points: an int32 device tensor [K, 3] of rows (collider a, collider b, group) - the full product of the colliders `a` names with
+        those `b` names, a-major, without the pairs of a collider with itself.  a, b: a name of collider_names, an object's name from visual_names (every collider of
+        the object), an index, or a sequence of those.  Lists of several groups: torch.cat."""
+        who = 'collider_pairs'
+        if isinstance(group, bool) or not isinstance(group, int) or not 0 <= group < _lib.CP_MAX_GROUPS:
+            raise ValueError('%s: group is an integer in 0 .. %d, not %r' % (who, _lib.CP_MAX_GROUPS - 1, group))
+        ca, cb = self._colliders_of(who, a), self._colliders_of(who, b)
+        rows = [(x, y, group) for x in ca for y in cb if x != y]
+        if not rows:
+            raise ValueError('%s: no pair is left (a and b name the same single collider)' % who)
+        return torch.tensor(rows, dtype=torch.int32, device=self.device).reshape(-1, 3)
+
+    def closest_points(self, pairs, states=None, index=None, max_distance=None, n_groups=0, out=None):
+        """bullet_client.getClosestPoints for K collider pairs of every live env or of stored state rows (rp_closest_points): a dict of device tensors 'distance'
+        float32 [M, K], 'point_a' / 'point_b' / 'normal' float32 [M, K, 3] (world; the normal from b toward a) and 'status' int32 [M, K]; with n_groups = G > 0 also
+        'group_min' float32 [M, G] and 'group_pair' int32 [M, G].  The shapes are the ray caster's, without margins: exact boxes, spheres, the links' convex hulls.
+
+        status: 0 separated (distance > 0, point_a - point_b = normal * distance); 1 overlap or touching (distance exactly 0, both points the common point, normal
+        zero - penetration depth is not reported); 2 far (only with max_distance > 0: the gap of the world boxes around the shapes exceeds it; distance =
+        max_distance, points and normal zero); 3 skipped (a collider number outside the model, a == b, or a bad row index: the pair's other outputs keep what they
+        held - zero in tensors made here); bit 4: the bounded iteration ended at its cap, the distance is an upper bound.
+
+        pairs: collider_pairs(...) - an int32 device tensor [K, 3] of (collider a, collider b, group), passed through unread - or a host list of such triples (or of
+        (a, b) pairs: group 0), which is range-checked here; 1 <= K <= 4096.  group_min / group_pair: per row and group the smallest distance over the group's pairs
+        that are not skipped (a far pair counts with max_distance) and that pair's index, the lowest among equals; +inf / -1 for an empty group.
+        states / index: as render_states' - a float32 device tensor [R, >= 128] of get_state() rows and an int32 device tensor [M] of rows to take (an entry outside
+        [0, R): every pair of that row is skipped); None: the live envs.  max_distance: None or <= 0: no cut.  out: a dict of tensors to write into (SKIPPED cells keep
+        their values).  Host values are checked (ValueError) before the library is touched; nothing is read back; the live envs are neither written nor disturbed."""
+        who = 'closest_points'
+        if torch.is_tensor(pairs) and pairs.is_cuda:
+            if not (pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 3):
+                raise ValueError('%s: pairs is an int32 tensor [K, 3], not %s %s' % (who, pairs.dtype, tuple(pairs.shape)))
+            pairs = pairs.contiguous()
+        else:
+            try:
+                rows = [[int(v) for v in p] for p in (pairs.tolist() if torch.is_tensor(pairs) else pairs)]
+            except (TypeError, ValueError):
+                raise ValueError('%s: pairs is an int32 device tensor [K, 3] or a list of (a, b) / (a, b, group), not %r' % (who, type(pairs).__name__)) from None
+            n_col = len(self.collider_names)
+            for p in rows:
+                if len(p) == 2:
+                    p.append(0)
+                if len(p) != 3:
+                    raise ValueError('%s: a pair is (a, b) or (a, b, group), not %r' % (who, tuple(p)))
+                if not (0 <= p[0] < n_col and 0 <= p[1] < n_col) or p[0] == p[1]:
+                    raise ValueError('%s: pair %r: colliders lie in 0 .. %d and differ' % (who, tuple(p[:2]), n_col - 1))
+                if not 0 <= p[2] < max(int(n_groups) if isinstance(n_groups, int) else 0, 1):
+                    raise ValueError('%s: pair %r: group %d lies outside 0 .. %d' % (who, tuple(p[:2]), p[2], max(int(n_groups), 1) - 1))
+            pairs = torch.tensor(rows, dtype=torch.int32).reshape(-1, 3)
+        k = int(pairs.shape[0])
+        if not 1 <= k <= _lib.CP_MAX_PAIRS:
+            raise ValueError('%s: pairs has %d rows, expected 1 .. %d' % (who, k, _lib.CP_MAX_PAIRS))
+        if isinstance(n_groups, bool) or not isinstance(n_groups, int) or not 0 <= n_groups <= _lib.CP_MAX_GROUPS:
+            raise ValueError('%s: n_groups is an integer in 0 .. %d, not %r' % (who, _lib.CP_MAX_GROUPS, n_groups))
+        if max_distance is None:
+            max_distance = 0.0
+        try:
+            max_distance = float(max_distance)
+        except (TypeError, ValueError):
+            raise ValueError('%s: max_distance is None or a number of metres, not %r' % (who, max_distance)) from None
+        if max_distance != max_distance:
+            raise ValueError('%s: max_distance is None or a number of metres, not NaN' % who)
+        if states is not None:
+            if not (torch.is_tensor(states) and states.dtype == torch.float32 and states.dim() == 2):
+                raise ValueError('%s: states is None or a float32 tensor [R, >= 128], not %s' % (who, (states.dtype, tuple(states.shape)) if torch.is_tensor(states)
+                                                                                                 else type(states).__name__))
+            if states.shape[0] < 1 or states.shape[1] < 128:
+                raise ValueError('%s: states has at least one row of at least 128 floats (the 512-byte state record), not %s' % (who, tuple(states.shape)))
+            if states.stride(1) != 1 or states.stride(0) < 128:
+                raise ValueError('%s: the last dimension of states is contiguous and its rows lie at least 128 floats apart, not strides %s' % (who, tuple(states.stride())))
+            if not states.is_cuda:
+                raise ValueError('%s: states is a device tensor, not one on %s' % (who, states.device))
+        n_rows = self.num_envs if states is None else int(states.shape[0])
+        if index is not None and not (torch.is_tensor(index) and index.dtype == torch.int32 and index.dim() == 1 and index.is_cuda):
+            raise ValueError('%s: index is None or an int32 device tensor [M], not %s' % (who, (index.dtype, tuple(index.shape), str(index.device)) if torch.is_tensor(index)
+                                                                                          else type(index).__name__))
+        m = n_rows if index is None else int(index.shape[0])
+        if m < 1:
+            raise ValueError('%s: no row to query (index is empty)' % who)
+        shapes = {'distance': ((m, k), torch.float32), 'point_a': ((m, k, 3), torch.float32), 'point_b': ((m, k, 3), torch.float32),
+                  'normal': ((m, k, 3), torch.float32), 'status': ((m, k), torch.int32)}
+        if n_groups > 0:
+            shapes.update({'group_min': ((m, n_groups), torch.float32), 'group_pair': ((m, n_groups), torch.int32)})
+        if out is not None and (not isinstance(out, dict) or set(out) - set(shapes)):
+            raise ValueError('%s: out is a dict with keys among %s' % (who, ', '.join(shapes)))
+        for key, t in (out or {}).items():
+            shape, dtype = shapes[key]
+            if t is not None and not (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.is_cuda):
+                raise ValueError('%s: out[%r] is a contiguous %s device tensor %s, not %s' % (who, key, dtype, shape, (t.dtype, tuple(t.shape), str(t.device))
+                                                                                             if torch.is_tensor(t) else type(t).__name__))
+        res = {}
+        for key, (shape, dtype) in shapes.items():
+            t = out.get(key) if out is not None else None
+            res[key] = t if t is not None else torch.zeros(shape, dtype=dtype, device=self.device)
+        pairs = pairs.to(self.device)
+        index = index.contiguous() if index is not None else None
+        src = _lib.RpStateRows(_ptr(states), 4 * states.stride(0) if states is not None else 0, n_rows, _ptr(index), None)
+        self._call('rp_closest_points', C.byref(src), m, _ptr(pairs), k, n_groups, max_distance, _ptr(res['distance']), _ptr(res['point_a']), _ptr(res['point_b']),
+                   _ptr(res['normal']), _ptr(res['status']), _ptr(res.get('group_min')), _ptr(res.get('group_pair')), self._stream())
+        self._kept['rp_closest_points'] = (pairs, index, states)      # (kept until the next call: the kernel reads them when the stream gets there)
+        return res
 
     def get_state(self):
         n = self.lib.rp_state_bytes(self.h) // 4
