@@ -125,6 +125,8 @@ def load(f32=False, bullet_ref=False, abx=False):
     lib.rpo_mass_matrix_inv.argtypes = [vp, dp]
     lib.rpo_forward_dynamics.argtypes = [vp, dp]
     lib.rpo_contacts.argtypes = [vp, dp, C.c_int]
+    lib.rpo_unconstrained_velocities.argtypes = [vp, dp]
+    lib.rpo_last_contacts_of.argtypes = [vp, C.c_int, C.c_int]
     lib.rpo_last_num_rows.argtypes = [vp]
     lib.rpo_contact_substeps.argtypes = [vp]
     lib.rpo_residual_substeps.argtypes = [vp]
@@ -511,6 +513,20 @@ class OracleEnv:
         a = np.zeros(self.n_arm)
         self.lib.rpo_forward_dynamics(self.h, a.ctypes.data_as(C.POINTER(C.c_double)))
         return a
+
+    def unconstrained_velocities(self):
+        """v* = v + dt a of every dof (arm, free bodies' linear and angular, scene joints) at the current state, before any row"""
+        v = np.zeros(self.nv)
+        self.lib.rpo_unconstrained_velocities(self.h, v.ctypes.data_as(C.POINTER(C.c_double)))
+        return v
+
+    def last_contacts_of(self, body_lo, body_hi):
+        """how many contacts of the latest contact list (contacts() or a substep's) touch a body numbered body_lo .. body_hi (0 the static world, 1 .. n_arm the arm's
+        links, then the free bodies, then the scene-joint bodies)"""
+        return self.lib.rpo_last_contacts_of(self.h, int(body_lo), int(body_hi))
+
+    def last_arm_contacts(self):
+        return self.last_contacts_of(1, self.n_arm)
 
     def contacts(self, max_n=96):
         """[n, 9]: collider a, collider b, point, normal (from b toward a), distance.  Mode B: the points of its persistent manifolds (this call advances

@@ -3096,6 +3096,23 @@ void rpo_forward_dynamics(rpo_env* e, double* qdd) {
   for (int i = 0; i < e->m.n_arm; i++) qdd[i] = a[i];
 }
 
+/* the unconstrained velocities v* = v + dt a of every dof at the current state (substep_unconstrained alone: no collision phase, no rows) */
+void rpo_unconstrained_velocities(rpo_env* e, double* vstar) {
+  real vs[RP_MAX_NV] = {0};
+  update_transforms(e);
+  substep_unconstrained(e, vs);
+  for (int i = 0; i < e->nv; i++) vstar[i] = vs[i];
+}
+/* contacts of the latest contact list that touch a body numbered body_lo .. body_hi (1 .. n_arm: the arm's links) */
+int rpo_last_contacts_of(const rpo_env* e, int body_lo, int body_hi) {
+  int n = 0;
+  for (int i = 0; i < e->ncon; i++) {
+    const int a = e->m.col_body[e->con[i].ca], b = e->m.col_body[e->con[i].cb];
+    n += (a >= body_lo && a <= body_hi) || (b >= body_lo && b <= body_hi);
+  }
+  return n;
+}
+
 int rpo_contacts(rpo_env* e, double* out, int max) {
   update_transforms(e);
   collide(e);

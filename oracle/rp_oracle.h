@@ -130,6 +130,8 @@ void rpo_clear_quat_memory(rpo_env*);
 void rpo_site_pose(const rpo_env*, int site, double* pos, double* quat, double* linvel, double* angvel);
 void rpo_mass_matrix_inv(rpo_env*, double* Minv /* nv*nv, arm block via unit impulse responses */);
 void rpo_forward_dynamics(rpo_env*, double* qdd /* n_arm */);
+void rpo_unconstrained_velocities(rpo_env*, double* vstar /* nv: v + dt a of every dof at the current state, before any row */);
+int rpo_last_contacts_of(const rpo_env*, int body_lo, int body_hi);      /* contacts of the latest contact list that touch a body numbered body_lo .. body_hi (1 .. n_arm: the arm) */
 int rpo_contacts(rpo_env*, double* out /* per contact: colA colB px py pz nx ny nz dist */, int max);
 int rpo_last_num_tors(const rpo_env* e);        /* torsional friction rows of the latest substep */
 void rpo_last_collide_counts(const rpo_env* e, int* out /* 5 */);     /* what the latest collision phase wanted before its caps: overlapping pairs, candidates, manifolds, contacts, torsional rows */

@@ -1452,7 +1452,8 @@ class VecPlayEnv:
         self._call('rp_set_debug_flags', int(flags))
 
     def debug_row_counts(self):
-        """test hook: per env of the latest substep, [unit rows, contacts, 1 if an arm contact, spanning contacts] (host tensor)"""
+        """test hook: per env of the latest substep, [unit rows, contacts, 1 if a contact in the arm's half of the velocity layout (arm links, and the
+        rotation-locked drawer where the model has one: it rests on its rails), spanning contacts] (host tensor)"""
         buf = (C.c_int32 * (2 * self.num_envs))()
         self._call('rp_debug_row_counts', buf)
         a = torch.tensor(list(buf), dtype=torch.int64).reshape(self.num_envs, 2)
